@@ -10,7 +10,12 @@ preconditioning, residual, restriction, coarse solve, prolongation, post
 pcg) on the global grid, slab-decomposed over N GPUs (strong scaling).  Rank 0
 prints ONE JSON line.
 
-Reported beside the headline ``value`` (V-cycle DOF/s, whole job):
+A plain run sets up, runs the W untimed and the K timed cycles and prints the
+headline ``value`` (V-cycle DOF/s, whole job) with ``ms_per_step``;
+``--dump-outputs DIR`` also writes what the last timed cycle returned (the
+iterate, or a fixed seeded sample of it, and the pcg infos) as ``DIR/*.npy``.
+
+With ``--full`` the line also reports, beside the headline:
 * ``roofline`` -- the dominant kernel (the fused Kron-apply + damped-Jacobi
   sweep, 24 algorithmic B/DOF) timed per launch with HIP events on the launch
   stream inside the timed region, against 8 TB/s;
@@ -69,9 +74,17 @@ def parse():
                     help="tools/pmc_traffic.py summary of a separate rocprofv3 --pmc pass "
                          "(FETCH_SIZE x2 + WRITE_SIZE per launch) used for roofline.traffic; used only "
                          "when its recorded p and kernel variant are this run's")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-launch roofline sample of "
+                         "the Jacobi sweep inside the timed cycles, the isolated Kron mat-vec and the CPU baseline")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed cycles write what the last one returned as DIR/<name>.npy (float64): the "
+                         "iterate x (a fixed seeded sample of it above 32 MB) and the pre/post pcg info")
     a = ap.parse_args()
     if a.steps is None:
         a.steps = 3 if a.ndim == 3 else 50
+    if a.steps < 1 or (a.warmup is not None and a.warmup < 0):
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.warmup is None:
         # 2D: a cycle takes ~3.5 ms, and 5 untimed cycles left the GPU's clocks / the
         # host's state short of steady: 3.96-5.84 ms per cycle measured after 5, 3.44-3.59
@@ -141,21 +154,88 @@ def main():
     for _ in range(args.warmup):
         mg.cycle(bf)
     barrier()
-    # HIP events around every --timing-every-th (default 4th) Jacobi launch of the timed region (a host event record
-    # costs a few us: a sample keeps the measured cycle unperturbed)
-    A.timing(True, "jacobi", every=args.timing_every, reserve=64 * args.steps + 64)
+    if args.full:
+        # HIP events around every --timing-every-th (default 4th) Jacobi launch of the timed region (a host event
+        # record costs a few us: a sample keeps the measured cycle unperturbed)
+        A.timing(True, "jacobi", every=args.timing_every, reserve=64 * args.steps + 64)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         x, ipre, ipos = mg.cycle(bf)
     barrier()
     dt = time.perf_counter() - t0
-    sweep_total_s, n_sweeps, sweep_dofs = A.timing_read("jacobi")
-    A.timing(False)
+    if args.full:
+        sweep = A.timing_read("jacobi")   # (seconds, launches, output DOFs)
+        A.timing(False)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     sec_per_cycle = dt / args.steps
+    if args.dump_outputs:
+        dump_outputs(Path(args.dump_outputs), mg.space.interior(x._data), ipre, ipos, rank if world > 1 else None)
+    side = side_measurements(args, mg, barrier, world, rank, local_dof, sweep) if args.full else {}
+
+    if rank == 0:
+        gdof = mg.ndof
+        out = {
+            # BASELINE's metric names the headline 3D p = 3 config; other configs say theirs
+            "metric": METRIC.replace("3D Poisson p=3", f"{nd}D Poisson p={args.p}"),
+            "value": gdof / sec_per_cycle,
+            "unit": "DOF/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": sec_per_cycle * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic: b = 1 RHS (sources/mg_jac.py:57-62), uniform open knots, assembled -Δu+u factors",
+            "config": {
+                "workload": (f"two-level V-cycle, {nd}D -Δu+u, p={args.p}, {args.cells}^{nd} cells ({n}^{nd} DOF), "
+                             f"coarse {args.coarse}^{nd} cells, pre/post pcg(tol=1e-6, maxiter=10) + damped Jacobi; "
+                             f"the reference's discarded mat-vec s = A.dot(r) (sources/solvers.py:109, one per pcg "
+                             f"iteration) is not computed on the GPU (the CPU baseline keeps it)"),
+                "global_dof": gdof, "ndim": nd, "p": args.p, "cells": args.cells, "coarse_cells": args.coarse,
+                "parallelism": parallelism,
+            },
+            "comm": transport,
+            **({"comm_note": comm_note} if comm_note else {}),
+            **side,
+            "solver": {"info_pre": ipre, "info_pos": ipos},
+        }
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, x, ipre, ipos, rank=None):
+    """``--dump-outputs``: what the last timed cycle returned, as float64 ``.npy`` files.
+    ``x`` is the iterate's owned entries (a device view); above 32 MB a fixed sample of
+    2^22 entries (flat C-order positions drawn once from a seeded generator, sorted) is
+    written instead, the same positions in every run of the same configuration."""
+    import numpy as np
+    import torch
+    out_dir.mkdir(parents=True, exist_ok=True)
+    tag = "" if rank is None else f"_rank{rank}"
+    if x.numel() * 8 <= 32 << 20:
+        xs = x.cpu().numpy()
+    else:
+        flat = np.sort(np.random.default_rng(20240607).integers(0, x.numel(), size=1 << 22))
+        idx = np.unravel_index(flat, tuple(x.shape))
+        xs = x[tuple(torch.from_numpy(i).to(x.device) for i in idx)].cpu().numpy()
+    np.save(out_dir / f"x{tag}.npy", np.ascontiguousarray(xs, dtype=np.float64))
+    info = [[float(i["niter"]), float(i["success"]), float(i["res_norm"])] for i in (ipre, ipos)]
+    np.save(out_dir / f"pcg_info{tag}.npy", np.asarray(info, dtype=np.float64))   # rows pre, post: niter, success, res_norm
+
+
+def side_measurements(args, mg, barrier, world, rank, local_dof, sweep):
+    """``--full``: the roofline figures of the Jacobi launches sampled in the timed cycles
+    (``sweep``), the isolated Kron mat-vec and the CPU baseline; entries of the result line."""
+    import torch
+    import torch.distributed as dist
+    A, nd = mg.A, args.ndim
+    sweep_total_s, n_sweeps, sweep_dofs = sweep
 
     # per-launch kernel durations inside the timed region (events on the launch stream);
     # one operator call is 1 launch, or 2 when the halo exchange overlaps the interior planes
@@ -242,50 +322,21 @@ def main():
         except Exception as e:  # baseline is informative only
             cpu = {"value": None, "unit": "DOF/s", "cores": 0, "kind": "port", "sample": f"failed: {e!r}"}
 
-    if rank == 0:
-        gdof = mg.ndof
-        out = {
-            # BASELINE's metric names the headline 3D p = 3 config; other configs say theirs
-            "metric": METRIC.replace("3D Poisson p=3", f"{nd}D Poisson p={args.p}"),
-            "value": gdof / sec_per_cycle,
-            "unit": "DOF/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": sec_per_cycle * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic: b = 1 RHS (sources/mg_jac.py:57-62), uniform open knots, assembled -Δu+u factors",
-            "config": {
-                "workload": (f"two-level V-cycle, {nd}D -Δu+u, p={args.p}, {args.cells}^{nd} cells ({n}^{nd} DOF), "
-                             f"coarse {args.coarse}^{nd} cells, pre/post pcg(tol=1e-6, maxiter=10) + damped Jacobi; "
-                             f"the reference's discarded mat-vec s = A.dot(r) (sources/solvers.py:109, one per pcg "
-                             f"iteration) is not computed on the GPU (the CPU baseline keeps it)"),
-                "global_dof": gdof, "ndim": nd, "p": args.p, "cells": args.cells, "coarse_cells": args.coarse,
-                "parallelism": parallelism,
-            },
-            "comm": transport,
-            **({"comm_note": comm_note} if comm_note else {}),
-            "roofline": {
-                "kernel": f"{KERNEL_NAMES.get(jac_v, f'variant {jac_v}')}<P={args.p},{nd}D,SUM,JACOBI> (Kron apply + damped-Jacobi update)",
-                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                "algorithmic_bytes_per_launch": bytes_sweep, "avg_launch_us": sweep_s * 1e6,
-                "launches_timed": n_sweeps,
-            },
-            "kron_spmv": {"kernel": f"{KERNEL_NAMES.get(app_v, f'variant {app_v}')}<P={args.p},{nd}D,SUM,APPLY>",
-                          "mall_flush_mib": args.flush_mall,
-                          "achieved": kron_gbps, "unit": "GB/s", "frac": kron_gbps / HBM_PEAK_GBPS,
-                          "median_launch_us": kron_s * 1e6, "mean_launch_us": kron_mean_s * 1e6,
-                          "bytes_per_dof": 16, "launches": args.kron_reps, "untimed_warmup_launches": args.kron_warm},
-            "cpu_baseline": cpu,
-            "solver": {"info_pre": ipre, "info_pos": ipos},
-        }
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return {
+        "roofline": {
+            "kernel": f"{KERNEL_NAMES.get(jac_v, f'variant {jac_v}')}<P={args.p},{nd}D,SUM,JACOBI> (Kron apply + damped-Jacobi update)",
+            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+            "algorithmic_bytes_per_launch": bytes_sweep, "avg_launch_us": sweep_s * 1e6,
+            "launches_timed": n_sweeps,
+        },
+        "kron_spmv": {"kernel": f"{KERNEL_NAMES.get(app_v, f'variant {app_v}')}<P={args.p},{nd}D,SUM,APPLY>",
+                      "mall_flush_mib": args.flush_mall,
+                      "achieved": kron_gbps, "unit": "GB/s", "frac": kron_gbps / HBM_PEAK_GBPS,
+                      "median_launch_us": kron_s * 1e6, "mean_launch_us": kron_mean_s * 1e6,
+                      "bytes_per_dof": 16, "launches": args.kron_reps, "untimed_warmup_launches": args.kron_warm},
+        "cpu_baseline": cpu,
+    }
 
 
 if __name__ == "__main__":

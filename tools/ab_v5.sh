@@ -20,7 +20,7 @@ done
 [ -n "${AB_NOBENCH:-}" ] && exit 0
 for L in "$@"; do
   tag=$(basename $L .so)
-  POMS_HIP_LIB=$PWD/$L timeout -k 10 600 python -u bench.py --no-cpu-baseline > $O/bench_$tag.log 2>&1
+  POMS_HIP_LIB=$PWD/$L timeout -k 10 600 python -u bench.py --full --no-cpu-baseline > $O/bench_$tag.log 2>&1
   rc=$?; echo "$tag bench rc=$rc"; tail -1 $O/bench_$tag.log | cut -c1-300
   [ $rc -eq 0 ] || exit $rc
 done

@@ -36,17 +36,17 @@ for step in "$@"; do
         tests) run pytest_gpu 1500 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread -p no:cacheprovider -rf ;;
         pytest:*) a=${step#pytest:}; run pytest_$i 900 python -u -m pytest ${a//,/ } -x -v --timeout 300 --timeout-method thread -p no:cacheprovider -rf ;;
         smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench) run bench 600 python bench.py ;;
-        bench2d) run bench_2d 300 python bench.py --ndim 2 --no-cpu-baseline ;;
+        bench) run bench 600 python bench.py --full ;;
+        bench2d) run bench_2d 300 python bench.py --full --ndim 2 --no-cpu-baseline ;;
         bench:*) a=${step#bench:}; run bench_$i 600 python bench.py ${a//,/ } ;;
         kb:*) a=${step#kb:}; run kb_$i 600 python tools/kernel_bench.py ${a//,/ } ;;
         py:*) a=${step#py:}; run py_$i 600 python ${a//,/ } ;;
         proxy) run proxy_loop_r1 300 python tools/slab_proxy.py --loopback-rank 1 --world 8 --steps 5 ;;
         prof) (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o run -- \
-                  python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline) > $O/prof.log 2>&1
+                  python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline) > $O/prof.log 2>&1
               rc=$?; echo "prof rc=$rc"; [ $rc -eq 0 ] || stop prof $rc ;;
         prof2d) (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof2d -o run -- \
-                  python3 $R/bench.py --ndim 2 --steps 10 --warmup 3 --no-cpu-baseline) > $O/prof2d.log 2>&1
+                  python3 $R/bench.py --full --ndim 2 --steps 10 --warmup 3 --no-cpu-baseline) > $O/prof2d.log 2>&1
               rc=$?; echo "prof2d rc=$rc"; [ $rc -eq 0 ] || stop prof2d $rc ;;
         pmc:*) IFS=: read -r _ ptag kern kargs <<< "$step"
                run pmc_$ptag 600 bash tools/pmc_traffic.sh $ptag "$kern" ${kargs//,/ } ;;
