@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define POMS_ABI_VERSION 3
+#define POMS_ABI_VERSION 4 /* 4: poms_pcg_opts.skip_tail, poms_pcg_final_update_dev */
 
 /* operator forms (see poms_op_create) */
 #define POMS_FORM_SINGLE 0 /* y = F0 (x) F1 (x) F2 x                                  */
@@ -316,6 +316,16 @@ int poms_pcg_r_update_dev(poms_ctx* ctx, const poms_layout* L, const double* alp
                           const double* q, double* out_dev, void* stream);
 int poms_pcg_xp_update_dev(poms_ctx* ctx, const poms_layout* L, const double* ab_dev, double* x, double* p,
                            const double* s, void* stream);
+/* pcg's last iteration when the rest of it is discarded (poms_pcg_opts.skip_tail):
+ * x += alpha p (the x half of poms_pcg_xp_update_dev, bitwise) and
+ * out_dev[0] = (r - alpha q).(r - alpha q) (poms_pcg_r_update_dev's sum, bitwise).
+ * r - alpha q is not kept.  r's buffer takes x_old + alpha p rounded as pcg's
+ * early-stop update rounds it (poms_vec_axpby_dev(1, x, alpha, p): the product, then
+ * the sum; 1 ulp from the fma in places): a caller whose stop test fires on this sum
+ * copies r over x and has the bits of the loop that was not cut short.         */
+int poms_pcg_final_update_dev(poms_ctx* ctx, const poms_layout* L, const double* alpha_dev, double* x,
+                              const double* p, double* r, const double* q, double* out_dev,
+                              void* stream);
 /* Reduce `count` partials from the context scratch into out_dev[0]. */
 int poms_reduce_partials(poms_ctx* ctx, int64_t count, double* out_dev, void* stream);
 /* Same, starting at scratch[offset]. */
@@ -526,6 +536,11 @@ typedef struct poms_pcg_opts {
     int jmaxiter;
     double omega;    /* 2/3                                                             */
     int prev, next;  /* slab neighbours (comm != NULL), -1: none                        */
+    int skip_tail;   /* 0: every launch of the reference's loop.  Non-zero: iteration
+                      * k == maxiter stops after x += alpha p and r.r -- the reference
+                      * still runs s = psolve(A, r), s.r, beta and p = s + beta p there
+                      * (`sources/solvers.py:117-124`) and returns without reading them.
+                      * The same x and info, one preconditioner call less.             */
 } poms_pcg_opts;
 typedef struct poms_pcg_info {
     int niter;

@@ -42,7 +42,7 @@ class Layout(C.Structure):
 
 class PcgOpts(C.Structure):
     _fields_ = [("tol", C.c_double), ("maxiter", C.c_int), ("jtol", C.c_double), ("jmaxiter", C.c_int),
-                ("omega", C.c_double), ("prev", C.c_int), ("next", C.c_int)]
+                ("omega", C.c_double), ("prev", C.c_int), ("next", C.c_int), ("skip_tail", C.c_int)]
 
 
 class PcgInfo(C.Structure):
@@ -107,6 +107,7 @@ _SIGS = {
     "poms_copy_to_host_async": [_vp, _vp, _vp, _i64, _vp],
     "poms_pcg_r_update_dev": [_vp, _LP, _vp, _vp, _vp, _vp, _vp],
     "poms_pcg_xp_update_dev": [_vp, _LP, _vp, _vp, _vp, _vp, _vp],
+    "poms_pcg_final_update_dev": [_vp, _LP, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "poms_op_apply": [_vp, _vp, _vp, _i64, _i64, _vp],
     "poms_op_residual": [_vp, _vp, _vp, _vp, _i64, _i64, _vp],
     "poms_op_apply_dot": [_vp, _vp, _vp, _i64, _i64, _vp],

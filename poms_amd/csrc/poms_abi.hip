@@ -71,7 +71,7 @@ int band_lu(int64_t n, int kl, int ku, double* ab, int64_t ldab, int* ipiv);
 void band_lu_tables(int64_t n, int kl, int ku, const double* ab, int64_t ldab, const int* ipiv,
                     std::vector<double>& L, std::vector<double>& U, std::vector<int>& piv);
 
-enum { V_AXPBY = 0, V_SCALE = 1, V_FILL = 2, V_DOT = 3, V_PCGUPD = 4, V_RUPD = 5, V_XPUPD = 6, V_SCALEDOT = 7 };   // (vec_ops.hip's VecOp)
+enum { V_AXPBY = 0, V_SCALE = 1, V_FILL = 2, V_DOT = 3, V_PCGUPD = 4, V_RUPD = 5, V_XPUPD = 6, V_SCALEDOT = 7, V_FINUPD = 8 };   // (vec_ops.hip's VecOp)
 
 }  // namespace poms
 
@@ -1331,7 +1331,7 @@ static int vec_common(poms_ctx* ctx, const poms_layout* L, int op, double a, dou
     if (!ctx || !layout_ok(L)) { set_error("vector op: bad context or layout"); return 1; }
     const RowGeom g = row_geom(L);
     int nb = 0;
-    const bool red = (op == V_DOT || op == V_PCGUPD || op == V_RUPD);
+    const bool red = (op == V_DOT || op == V_PCGUPD || op == V_RUPD || op == V_FINUPD);
     // whole interior planes as one flat range (ghost rows / columns are zero in every
     // vector and stay zero -- unless the layout says they hold a neighbour's data);
     // the per-row kernel for fills, mixed alignments and ghost data
@@ -1436,6 +1436,16 @@ int poms_pcg_xp_update_dev(poms_ctx* ctx, const poms_layout* L, const double* ab
                            const double* s, void* stream) {
     if (!x || !p || !s || !ab_dev) { set_error("pcg_xp_update_dev: null argument"); return 1; }
     return vec_common(ctx, L, V_XPUPD, 0.0, 0.0, s, nullptr, x, p, nullptr, nullptr, stream, ab_dev);
+}
+
+// pcg's last iteration when what follows it is discarded (poms_pcg_opts.skip_tail):
+// x += alpha p with V_XPUPD's statement, (r - alpha q).(r - alpha q) with V_RUPD's.
+// r - alpha q is not kept: r's buffer takes x as the early-stop update would have
+// rounded it (vec_ops.hip: stop_update), for the caller whose stop test then fires
+int poms_pcg_final_update_dev(poms_ctx* ctx, const poms_layout* L, const double* alpha_dev, double* x,
+                              const double* p, double* r, const double* q, double* out_dev, void* stream) {
+    if (!x || !p || !r || !q || !out_dev || !alpha_dev) { set_error("pcg_final_update_dev: null argument"); return 1; }
+    return vec_common(ctx, L, V_FINUPD, 0.0, 0.0, nullptr, p, x, r, q, out_dev, stream, alpha_dev);
 }
 
 int poms_reduce_partials(poms_ctx* ctx, int64_t count, double* out_dev, void* stream) {
@@ -2411,8 +2421,11 @@ struct PcgRun {
     // r -= alpha q, r.r -> host slot h.  One rank: the flat kernel writes its per-block
     // partials straight into the slot's host region (the host adds them in the order
     // of the device reduction it replaces, so the same bits) -- one launch less per
-    // pcg iteration
-    int rupd(double* r, const double* q, int h) {
+    // pcg iteration.
+    // With x and p (skip_tail's last iteration): the final pass instead -- x += alpha p as
+    // well, r - alpha q not kept (V_FINUPD); the same count, head, grid and per-thread
+    // order, so the partials and r.r are the r update's bits.
+    int rupd(double* r, const double* q, int h, double* x = nullptr, const double* p = nullptr) {
         if (direct() && !(op->L.flags & POMS_LAYOUT_GHOST_DATA)) {
             const RowGeom g = row_geom(&op->L);
             const int64_t off = (int64_t)g.pd0 * g.s0, count = (int64_t)g.n0 * g.s0;
@@ -2437,8 +2450,9 @@ struct PcgRun {
                 } else if (flush_alpha()) {
                     return 1;
                 }
-                if (vec_flat_launch(V_RUPD, count, 0.0, 0.0, nullptr, nullptr, nullptr, r + off, q + off, reg, st, &nb,
-                                    sc + SC_ALPHA, af.part ? &af : nullptr) == 0) {
+                if (vec_flat_launch(x ? V_FINUPD : V_RUPD, count, 0.0, 0.0, nullptr, x ? p + off : nullptr,
+                                    x ? x + off : nullptr, r + off, q + off, reg, st, &nb, sc + SC_ALPHA,
+                                    af.part ? &af : nullptr) == 0) {
                     if (af.part) sr_stale = false;
                     alpha_part = nullptr;
                     POMS_HIP_CHECK(hipGetLastError());
@@ -2450,8 +2464,11 @@ struct PcgRun {
         }
         if (flush_alpha()) return 1;
         double* d = hslot(h);
-        if (!d || poms_pcg_r_update_dev(op->ctx, &op->L, sc + SC_ALPHA, r, q, d, stv) || lazy_post(h, 1)) return 1;
-        return 0;
+        if (!d) return 1;
+        if (x ? poms_pcg_final_update_dev(op->ctx, &op->L, sc + SC_ALPHA, x, p, r, q, d, stv)
+              : poms_pcg_r_update_dev(op->ctx, &op->L, sc + SC_ALPHA, r, q, d, stv))
+            return 1;
+        return lazy_post(h, 1);
     }
     int diag_scale_norm(const double* b, double* x, int h) {   // x = omega b / diag, ||x||^2 -> host slot h
         if (direct() && op->form != FORM_STENCIL) {   // partials straight into slot h's host region
@@ -2745,6 +2762,10 @@ static int spec_issue(PcgRun& R, const double* b, double* x, int has_x0, double*
         hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 0);
         const int vrr = R.svals(1);
         R.srr.push_back(vrr);
+        if (o->skip_tail && k == o->maxiter) {   // the rest of this iteration is discarded
+            if (poms_pcg_final_update_dev(ctx, L, R.sc + SC_ALPHA, x, p, r, q, op->spec_dev + vrr, stream)) return 1;
+            break;
+        }
         if (poms_pcg_r_update_dev(ctx, L, R.sc + SC_ALPHA, r, q, op->spec_dev + vrr, stream)) return 1;
         double* sn = nullptr;
         if (R.spec_damped_jacobi(r, fa, fb, SC_SRN, &sn)) return 1;
@@ -2813,7 +2834,7 @@ static int pcg_speculative(PcgRun& R, const double* b, double* x, int has_x0, do
     key[0] = (uint64_t)(uintptr_t)b;
     key[1] = (uint64_t)(uintptr_t)x;
     for (int i = 0; i < 5; ++i) key[2 + i] = (uint64_t)(uintptr_t)work[i];
-    key[7] = (uint64_t)has_x0 | ((uint64_t)(uint32_t)o->maxiter << 8) | ((uint64_t)(uint32_t)o->jmaxiter << 40);
+    key[7] = (uint64_t)has_x0 | ((uint64_t)(o->skip_tail ? 2 : 0)) | ((uint64_t)(uint32_t)o->maxiter << 8) | ((uint64_t)(uint32_t)o->jmaxiter << 40);
     key[8] = bits(o->tol);
     key[9] = bits(o->jtol);
     key[10] = bits(o->omega);
@@ -3033,6 +3054,18 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
     for (k = 1; k <= o->maxiter; ++k) {
         if (R.apd_alpha(p, q)) return 1;
         const int hrr = R.arm(H_RR, 1);
+        if (o->skip_tail && k == o->maxiter) {
+            // the reference goes on to s = psolve(A, r), s.r, beta and p (`sources/solvers.py:117-124`)
+            // and returns without reading any of them: x and r.r only
+            if (R.rupd(r, q, hrr, x, p)) return 1;
+            nrmr = R.get(hrr);
+            if (R.failed) return 1;
+            if (nrmr < o->tol * nrmr0) {   // x as the early-stop branch below rounds it: the final pass left it in r
+                if (poms_vec_scale(ctx, L, 1.0, r, x, stream)) return 1;
+                k -= 1;
+            }
+            break;
+        }
         if (R.rupd(r, q, hrr)) return 1;
         double* sn = nullptr;
         if (R.damped_jacobi(r, fa, fb, SC_SRN, &sn, &dd, fc)) return 1;   // queued before the read

@@ -12,7 +12,8 @@
 namespace poms {
 
 enum VecOp : int { V_AXPBY = 0, V_SCALE = 1, V_FILL = 2, V_DOT = 3, V_PCGUPD = 4, V_RUPD = 5, V_XPUPD = 6,
-                  V_SCALEDOT = 7 /* z = a x and z.z (flat kernel only) */ };
+                  V_SCALEDOT = 7 /* z = a x and z.z (flat kernel only) */,
+                  V_FINUPD = 8 /* pcg's last iteration, see stop_update */ };
 
 // grid caps (= partial sums per launch): the flat vector kernels run one pass per
 // thread up to 65536 blocks of 256 (grid-stride beyond): at 515^3 the r update
@@ -22,6 +23,18 @@ constexpr int kMaxPartials = 65536;
 constexpr int kMaxRowPartials = 4096;
 static_assert(kMaxPartials <= kScratch && kMaxRowPartials <= kScratch,
               "vector-kernel partials must fit the context scratch (advisor, round 3)");
+
+// V_FINUPD, the last pcg iteration when nothing after it is read: x += a*p with
+// V_XPUPD's fma and (r - a*q).(r - a*q) with V_RUPD's statements and order; r - a*q
+// itself is not kept.  If that sum then stops pcg, the loop would have formed x by
+// V_AXPBY(1, x, a, p) instead, which the compiler contracts to fma(1, x, a*p): the
+// product rounded, then the sum.  That value goes where r was (r is dead by then), so
+// the caller can take it without a pass that has to run before the sum is known.
+__device__ __forceinline__ double stop_update(double a, double p, double x) {
+#pragma clang fp contract(off)
+    const double t = a * p;
+    return x + t;
+}
 
 template <int OP>
 __global__ void __launch_bounds__(256)
@@ -58,6 +71,12 @@ vec_rows_kernel(const RowGeom g, double a, double b,
                 const double rn = fma(-a, q[o], w[o]);
                 w[o] = rn;
                 s = fma(rn, rn, s);
+            } else if constexpr (OP == V_FINUPD) {  // z = x += a*p (yv = p), r.r of r - a*q; w = stop_update
+                const double xo = z[o], po = yv[o];
+                z[o] = fma(a, po, xo);
+                const double rn = fma(-a, q[o], w[o]);
+                w[o] = stop_update(a, po, xo);
+                s = fma(rn, rn, s);
             } else {                                 // V_XPUPD: z = x += a*p_old; w = p = s + b*p_old (x = s)
                 const double po = w[o];
                 z[o] = fma(a, po, z[o]);
@@ -65,7 +84,7 @@ vec_rows_kernel(const RowGeom g, double a, double b,
             }
         }
     }
-    if constexpr (OP == V_DOT || OP == V_PCGUPD || OP == V_RUPD) {
+    if constexpr (OP == V_DOT || OP == V_PCGUPD || OP == V_RUPD || OP == V_FINUPD) {
         const double t = block_sum_256(s, red);
         if (threadIdx.x == 0) partial[blockIdx.x] = t;
     }
@@ -95,6 +114,12 @@ __device__ __forceinline__ void vec_elem(double a, double b, const double* x, co
         const double rn = fma(-a, q[o], w[o]);
         w[o] = rn;
         s = fma(rn, rn, s);
+    } else if constexpr (OP == V_FINUPD) {
+        const double xo = z[o], po = yv[o];
+        z[o] = fma(a, po, xo);
+        const double rn = fma(-a, q[o], w[o]);
+        w[o] = stop_update(a, po, xo);
+        s = fma(rn, rn, s);
     } else if constexpr (OP == V_XPUPD) {
         const double po = w[o];
         z[o] = fma(a, po, z[o]);
@@ -116,14 +141,14 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
     typedef double d2 __attribute__((ext_vector_type(2)));
     constexpr int U = 4;
     __shared__ double red[4];
-    if constexpr (OP == V_RUPD || OP == V_XPUPD) {
+    if constexpr (OP == V_RUPD || OP == V_XPUPD || OP == V_FINUPD) {
         if (af.part != nullptr) {   // alpha / beta from partials (see AlphaFold)
             double sp = 0.0;
             for (int i = threadIdx.x; i < af.n; i += 256) sp += af.part[i];
             const double t = block_sum_256(sp, red);
             if (threadIdx.x == 0) {
                 double v;
-                if constexpr (OP == V_RUPD) {   // t = p.q
+                if constexpr (OP != V_XPUPD) {   // t = p.q
                     v = af.sc[af.sr] / t;
                     if (blockIdx.x == 0) {
                         af.sc[1] = t;
@@ -142,7 +167,7 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
                 red[0] = v;
             }
             __syncthreads();
-            if constexpr (OP == V_RUPD) a = red[0];
+            if constexpr (OP != V_XPUPD) a = red[0];
             else b = red[0];
             __syncthreads();   // (red is the final reduction's again)
         }
@@ -166,10 +191,10 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
                 auto ld = [](const d2* ptr) { if constexpr (NTL) return __builtin_nontemporal_load(ptr); else return *ptr; };
                 if constexpr (OP == V_AXPBY || OP == V_SCALE || OP == V_DOT || OP == V_XPUPD || OP == V_SCALEDOT)
                     xa[u] = ld(X + i);
-                if constexpr (OP == V_AXPBY || OP == V_DOT || OP == V_PCGUPD) ya[u] = ld(Y + i);
-                if constexpr (OP == V_PCGUPD || OP == V_XPUPD) za[u] = ld(Z + i);
-                if constexpr (OP == V_PCGUPD || OP == V_RUPD || OP == V_XPUPD) wa[u] = ld(Wv + i);
-                if constexpr (OP == V_PCGUPD || OP == V_RUPD) qa[u] = ld(Q + i);
+                if constexpr (OP == V_AXPBY || OP == V_DOT || OP == V_PCGUPD || OP == V_FINUPD) ya[u] = ld(Y + i);
+                if constexpr (OP == V_PCGUPD || OP == V_XPUPD || OP == V_FINUPD) za[u] = ld(Z + i);
+                if constexpr (OP == V_PCGUPD || OP == V_RUPD || OP == V_XPUPD || OP == V_FINUPD) wa[u] = ld(Wv + i);
+                if constexpr (OP == V_PCGUPD || OP == V_RUPD || OP == V_FINUPD) qa[u] = ld(Q + i);
             }
         }
 #pragma unroll
@@ -203,6 +228,18 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
                     __builtin_nontemporal_store(rn, Wv + i);
                     s = fma(rn.x, rn.x, s);
                     s = fma(rn.y, rn.y, s);
+                } else if constexpr (OP == V_FINUPD) {   // x as V_XPUPD's, the sum as V_RUPD's
+                    d2 zn, rn, wn;
+                    zn.x = fma(a, ya[u].x, za[u].x);
+                    zn.y = fma(a, ya[u].y, za[u].y);
+                    __builtin_nontemporal_store(zn, Z + i);
+                    rn.x = fma(-a, qa[u].x, wa[u].x);
+                    rn.y = fma(-a, qa[u].y, wa[u].y);
+                    wn.x = stop_update(a, ya[u].x, za[u].x);
+                    wn.y = stop_update(a, ya[u].y, za[u].y);
+                    __builtin_nontemporal_store(wn, Wv + i);
+                    s = fma(rn.x, rn.x, s);
+                    s = fma(rn.y, rn.y, s);
                 } else {   // V_XPUPD
                     d2 zn, wn;
                     zn.x = fma(a, wa[u].x, za[u].x);
@@ -219,7 +256,7 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
         if (head) vec_elem<OP>(a, b, x, yv, z, w, q, 0, s);
         if (tail) vec_elem<OP>(a, b, x, yv, z, w, q, head + 2 * nd2, s);
     }
-    if constexpr (OP == V_DOT || OP == V_PCGUPD || OP == V_RUPD || OP == V_SCALEDOT) {
+    if constexpr (OP == V_DOT || OP == V_PCGUPD || OP == V_RUPD || OP == V_SCALEDOT || OP == V_FINUPD) {
         const double t = block_sum_256(s, red);
         if (threadIdx.x == 0) partial[blockIdx.x] = t;
     }
@@ -366,6 +403,7 @@ int vec_launch(int op, const RowGeom& g, double a, double b, const double* x, co
         POMS_VL(V_PCGUPD)
         POMS_VL(V_RUPD)
         POMS_VL(V_XPUPD)
+        POMS_VL(V_FINUPD)
 #undef POMS_VL
     }
     set_error("unknown vector op");
@@ -406,7 +444,7 @@ int zero_ghosts_launch(const RowGeom& g, double* z, hipStream_t st) {
 int vec_flat_launch(int op, int64_t count, double a, double b, const double* x, const double* y,
                     double* z, double* w, const double* q, double* partial, hipStream_t st,
                     int* nblk_out, const double* ab, const AlphaFold* af) {
-    const AlphaFold afv = (af != nullptr && (op == V_RUPD || op == V_XPUPD)) ? *af : AlphaFold{};
+    const AlphaFold afv = (af != nullptr && (op == V_RUPD || op == V_XPUPD || op == V_FINUPD)) ? *af : AlphaFold{};
     if (op == V_FILL || count < 4) return 1;
     int mis = -1;
     for (const void* ptr : {(const void*)x, (const void*)y, (const void*)z, (const void*)w, (const void*)q}) {
@@ -450,6 +488,7 @@ int vec_flat_launch(int op, int64_t count, double a, double b, const double* x, 
         POMS_VF(V_RUPD)
         POMS_VF(V_XPUPD)
         POMS_VF(V_SCALEDOT)
+        POMS_VF(V_FINUPD)
 #undef POMS_VF
     }
     return 1;

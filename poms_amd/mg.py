@@ -142,7 +142,8 @@ class TwoLevelVCycle:
     def cycle(self, bf: StencilVector, x0: StencilVector | None = None):
         """One V-cycle; returns ``(xf2, info_pre, info_pos)``."""
         A = self.A
-        xf, info_pre = pcg(A, damped_jacobi, bf, x0=x0, tol=self.tol, maxiter=self.maxiter)
+        # (_skip_tail: a smoother call's last iteration ends at x and r.r, see solvers.pcg)
+        xf, info_pre = pcg(A, damped_jacobi, bf, x0=x0, tol=self.tol, maxiter=self.maxiter, _skip_tail=True)
         if self.fused_restrict:
             rc = self.transfer.resid_restrict(A, bf, xf, out=self.rc)
         else:
@@ -153,10 +154,11 @@ class TwoLevelVCycle:
         xf.update_ghost_regions()
         if self.glt is not None:
             from .solvers import pcg_kron
-            xf2, info_pos = pcg_kron(A, self.glt, bf, x0=xf, tol=self.tol, maxiter=self.p + 1)
+            xf2, info_pos = pcg_kron(A, self.glt, bf, x0=xf, tol=self.tol, maxiter=self.p + 1, _skip_tail=True)
         else:
             # (xf is this cycle's own temporary: iterate in its buffer, no copy)
-            xf2, info_pos = pcg(A, damped_jacobi, bf, x0=xf, tol=self.tol, maxiter=self.maxiter, _x0_owned=True)
+            xf2, info_pos = pcg(A, damped_jacobi, bf, x0=xf, tol=self.tol, maxiter=self.maxiter, _x0_owned=True,
+                                _skip_tail=True)
         return xf2, info_pre, info_pos
 
 
@@ -255,7 +257,7 @@ class MultilevelVCycle:
 
     def _level(self, l: int, b: StencilVector, x0: StencilVector | None) -> StencilVector:
         A, tr = self.ops[l], self.transfers[l]
-        x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=self.maxiters[l])
+        x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True)
         if self.fused[l]:
             rc = tr.resid_restrict(A, b, x, out=self.rcs[l])
         else:
@@ -274,7 +276,7 @@ class MultilevelVCycle:
             ec = Vc.interior(ecv._data).contiguous().view(-1)
         tr.prolong_add(ec, x)
         x.update_ghost_regions()
-        x, ipos = pcg(A, damped_jacobi, b, x0=x, tol=self.tol, maxiter=self.maxiters[l])
+        x, ipos = pcg(A, damped_jacobi, b, x0=x, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True)
         if self.infos[l] is None:
             self.infos[l] = (ipre, ipos)
         return x

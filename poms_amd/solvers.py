@@ -19,6 +19,8 @@ Signatures, defaults, return conventions and stopping rules are those of
 
 Differences that do not change results:
 * the reference's discarded ``s = A.dot(r)`` (:109) is not computed;
+* with ``_skip_tail`` (the V-cycles' smoother calls) neither are ``psolve``, ``s.r``,
+  ``beta`` and ``p`` of iteration ``k == maxiter`` (:117-124), which nothing reads;
 * the per-element Python loop ``dr = omega*r/A[i,i,0,0]`` (:211-213) and the
   surrounding ``r = b - A.dot(x)``, ``x = x + dr``, ``dr.dot(dr)`` are one
   fused HIP kernel; the first sweep from ``x0 = None`` uses ``A.0 = 0``
@@ -60,19 +62,32 @@ def _print_header(title):
     print("+---------+---------------------+")
 
 
-def pcg(A, psolve, b, x0=None, tol=1e-6, maxiter=100, verbose=False, *, _x0_owned=False):
+def _tail_skipped(skip_tail) -> bool:
+    """``_skip_tail`` unless POMS_PCG_TAIL=1 asks for the reference's full last iteration
+    (read per call: an A/B of both in one process)."""
+    return bool(skip_tail) and os.environ.get("POMS_PCG_TAIL", "0") != "1"
+
+
+def pcg(A, psolve, b, x0=None, tol=1e-6, maxiter=100, verbose=False, *, _x0_owned=False, _skip_tail=False):
     """Preconditioned conjugate gradient (`sources/solvers.py:69-135`).
+
+    ``_skip_tail`` (internal: the V-cycles' smoother calls): iteration ``k == maxiter``
+    ends after ``x += alpha p`` and ``r.r``.  The reference goes on to ``s = psolve(A, r)``,
+    ``s.r``, ``beta`` and ``p = s + beta p`` (`sources/solvers.py:117-124`), leaves the
+    loop and returns ``x`` and ``info`` without reading any of them: the same result,
+    one preconditioner call less.
 
     ``_x0_owned`` (internal: the V-cycle's own temporaries) lets the native loop
     iterate in x0's buffer instead of a copy of it -- the reference copies x0
     (`sources/solvers.py:82`); a caller that never reads x0 again loses nothing."""
     _check(A, b)
     V = b.space
+    skip_tail = _tail_skipped(_skip_tail)
     if (psolve is damped_jacobi and not verbose and V.lazy_reductions and A.apply_dot_supported
             and A.fused_dot_supported):
         if _native_ok(A, V):
-            return _pcg_native(A, b, x0, tol, maxiter, _x0_owned)
-        return _pcg_device(A, b, x0, tol, maxiter)
+            return _pcg_native(A, b, x0, tol, maxiter, _x0_owned, skip_tail)
+        return _pcg_device(A, b, x0, tol, maxiter, skip_tail)
     ctx, lay = V.ctx, V.layout
     if x0 is None:
         x = V.zeros()
@@ -101,6 +116,16 @@ def pcg(A, psolve, b, x0=None, tol=1e-6, maxiter=100, verbose=False, *, _x0_owne
             A.dot(p, out=q)
             pq = p.dot(q)
         alpha = sr / pq
+        if skip_tail and k == maxiter:              # what follows would be discarded
+            import torch
+            a_dev = torch.tensor([alpha], dtype=x._data.dtype, device=x._data.device)
+            nrmr = V.global_dot(float(_pcg_final_update_dev(V, a_dev, x, p, r, q, local=True).item()))
+            if nrmr < tol * nrmr0:
+                x.assign(r)                         # (x as the early-stop update below rounds it)
+                k -= 1
+            elif verbose:
+                print(template.format(k, sqrt(nrmr)))
+            break
         nrmr = _pcg_r_update(V, alpha, r, q)        # r -= alpha q ; r.r
         if nrmr < tol * nrmr0:
             _vec(V, "poms_vec_axpby", 1.0, x, alpha, p, x)   # x += alpha p
@@ -121,7 +146,7 @@ def pcg(A, psolve, b, x0=None, tol=1e-6, maxiter=100, verbose=False, *, _x0_owne
     return x, info
 
 
-def _pcg_device(A, b, x0, tol, maxiter):
+def _pcg_device(A, b, x0, tol, maxiter, skip_tail=False):
     """pcg with damped_jacobi as psolve, scalars on the device.
 
     Same iterates and stopping rule as the host loop above (`sources/solvers.py:69-135`).
@@ -151,6 +176,12 @@ def _pcg_device(A, b, x0, tol, maxiter):
     for k in range(1, maxiter + 1):
         pq = A.dot_inner(p, q, device=True)
         alpha = sr / pq
+        if skip_tail and k == maxiter:                  # what follows would be discarded
+            nrmr = V.lazy_value(_pcg_final_update_dev(V, alpha, x, p, r, q)).value()
+            if nrmr < tol * nrmr0:
+                x.assign(r)                             # (x as the early-stop update below rounds it)
+                k -= 1
+            break
         nrm_dev = _pcg_r_update_dev(V, alpha, r, q)     # r -= alpha q ; r.r (device)
         pending = V.lazy_value(nrm_dev)
         srold = sr
@@ -178,7 +209,7 @@ def _native_ok(A, V) -> bool:
     return not V.is_distributed or V.dist.native is not None
 
 
-def _pcg_native(A, b, x0, tol, maxiter, x0_owned=False):
+def _pcg_native(A, b, x0, tol, maxiter, x0_owned=False, skip_tail=False):
     """pcg(A, damped_jacobi, b, x0, tol, maxiter) as one C call (``poms_pcg_jacobi``):
     the launches, device scalars and stop tests of :func:`_pcg_device`, bitwise the
     same iterates, without a Python round trip per launch."""
@@ -196,7 +227,7 @@ def _pcg_native(A, b, x0, tol, maxiter, x0_owned=False):
     d = V.dist if V.is_distributed else None
     opts = _lib.PcgOpts(float(tol), int(maxiter), 1e-6, 10, OMEGA,
                         -1 if d is None or d.prev is None else int(d.prev),
-                        -1 if d is None or d.next is None else int(d.next))
+                        -1 if d is None or d.next is None else int(d.next), 1 if skip_tail else 0)
     info = _lib.PcgInfo()
     ptrs = (C.c_void_p * 5)(*[w._data.data_ptr() for w in work])
     _lib.call("poms_pcg_jacobi", A._h, d.native.h if d is not None else None,
@@ -225,6 +256,20 @@ def _pcg_r_update_dev(V, alpha, r, q):
               rt.ptr(buf), rt.stream_handle())
     r._mark_written()
     return V.device_sum(buf[0:1])
+
+
+def _pcg_final_update_dev(V, alpha, x, p, r, q, local=False):
+    """x += alpha p and (r - alpha q).(r - alpha q) (device; ``local``: this rank's part).
+    r - alpha q is not kept: r takes x as pcg's early-stop update would have rounded it
+    (``poms_pcg_final_update_dev``), for the caller whose stop test fires on the sum."""
+    from . import _lib, runtime as rt
+    import ctypes as C
+    buf = V.scalar_buffer()
+    _lib.call("poms_pcg_final_update_dev", V.ctx, C.byref(V.layout), rt.ptr(alpha), rt.ptr(x._data), rt.ptr(p._data),
+              rt.ptr(r._data), rt.ptr(q._data), rt.ptr(buf), rt.stream_handle())
+    x._mark_written()
+    r._mark_written()
+    return buf[0:1] if local else V.device_sum(buf[0:1])
 
 
 def _pcg_xp_update_dev(V, ab, x, p, s):
@@ -406,20 +451,21 @@ def _damped_jacobi(A, b, x0=None, tol=1e-6, maxiter=10, verbose=False, want_dot=
     return x, dot
 
 
-def pcg_kron(A, factors, b, x0=None, tol=1e-6, maxiter=100, verbose=False):
+def pcg_kron(A, factors, b, x0=None, tol=1e-6, maxiter=100, verbose=False, *, _skip_tail=False):
     """PCG preconditioned by ``X = (F0^-1 ⊗ F1^-1 [⊗ F2^-1]) R`` (``factors[d]`` acts on
     axis ``d``): the body of `sources/solvers.py:239-306` for any dimension."""
     from .kron_solve import solver_for
     ks = solver_for(b.space, tuple(factors))
-    return pcg(A, lambda _A, r: ks.solve(r), b, x0=x0, tol=tol, maxiter=maxiter, verbose=verbose)
+    return pcg(A, lambda _A, r: ks.solve(r), b, x0=x0, tol=tol, maxiter=maxiter, verbose=verbose,
+               _skip_tail=_skip_tail)
 
 
-def pcg_glt(A, M1, M2, b, x0=None, tol=1e-6, maxiter=100, verbose=False):
+def pcg_glt(A, M1, M2, b, x0=None, tol=1e-6, maxiter=100, verbose=False, *, _skip_tail=False):
     """GLT-preconditioned CG (`sources/solvers.py:239-306`).  As the reference, the
     preconditioner is ``kron_solve_par(M2, M1, r)`` (:258, :290): M2 acts on axis 0."""
     if b.space.ndim != 2:
         raise ValueError("pcg_glt is the 2D solver of the reference; use pcg_kron for other dimensions")
-    return pcg_kron(A, (M2, M1), b, x0=x0, tol=tol, maxiter=maxiter, verbose=verbose)
+    return pcg_kron(A, (M2, M1), b, x0=x0, tol=tol, maxiter=maxiter, verbose=verbose, _skip_tail=_skip_tail)
 
 
 def crl(A, b, x0=None, tol=1e-5, maxiter=1000, verbose=False):
