@@ -563,6 +563,46 @@ int poms_op_timing(poms_op* op, int enable, int epilogue, int every, int reserve
 int poms_op_spec_stats(poms_op* op, int* stats);
 int poms_op_timing_read(poms_op* op, int epilogue, double* total_ms, int64_t* launches, int64_t* dofs);
 
+/* ---- spline fields on tensor point grids --------------------------------------- */
+/* Evaluation of the spline of a coefficient vector at a tensor grid of points, the
+ * load vector of a function given at the points, and the weighted squared error --
+ * what the reference leaves to a placeholder right-hand side (`sources/mg_jac.py:57-62`).
+ * Per axis d (HOST arrays, all three axes; an unused leading axis has n = 1, p = 0,
+ * one point, first = {0}, basis = {1, 0}, weight 1, qlo = {0}, qhi = {1}):
+ *   npts[d]    points Q_d (non-decreasing), p[d] the degree (0..5);
+ *   first[d]   (Q_d) index of the first non-zero basis function at point q (span - p);
+ *   basis[d]   (Q_d, p+1, 2) value and first derivative of function first[q] + a at q;
+ *   weights[d] (Q_d) quadrature weights -- `weights` NULL: a grid to evaluate on only;
+ *   qlo[d], qhi[d] (layout->n[d]) the contiguous points [qlo[i], qhi[i]) inside the
+ *              support of basis function i (non-decreasing) -- NULL: no load vector.
+ * The handle owns the device tables and every intermediate of a chunk of at most
+ * max_chunk_q0 axis-0 points; the calls below allocate, free and synchronise nothing.
+ * Distributed (slab) spaces are not supported: layout->n[0] is the global extent.   */
+typedef struct poms_field poms_field;
+int poms_field_create(poms_ctx* ctx, int ndim, const poms_layout* layout, const int64_t* npts, const int* p,
+                      const int* const* first, const double* const* basis, const double* const* weights,
+                      const int* const* qlo, const int* const* qhi, int64_t max_chunk_q0, poms_field** field);
+int poms_field_destroy(poms_field* field);
+/* out[q0 - q0b, q1, q2] = sum_a B0[q0, a0] B1[q1, a1] B2[q2, a2] x[first0 + a0, first1 + a1,
+ * first2 + a2] for q0 in [q0b, q0e) (at most max_chunk_q0 of them).  x: DEVICE padded
+ * vector of `layout`; out: DEVICE dense C-order (q0e - q0b, Q1, Q2) block, written once.
+ * der[d] in {0, 1}: value or first derivative along axis d.                          */
+int poms_field_eval(poms_field* field, const double* x, const int* der, int64_t q0b, int64_t q0e, double* out,
+                    void* stream);
+/* b[i] (+)= sum_q w0 w1 w2 B0[q0, .] B1[q1, .] B2[q2, .] f[q0 - q0b, q1, q2] over the points
+ * of [q0b, q0e) x Q1 x Q2 inside the support of i.  f: DEVICE dense block as `out` above;
+ * b: DEVICE padded vector.  One thread owns one b[i] (no atomics: the bits depend on the
+ * chunking only).  accumulate = 0 overwrites the interior (0 where no point of the range
+ * reaches); ghost cells and dead pitch columns are not written.  Needs weights, qlo, qhi. */
+int poms_field_load(poms_field* field, const double* f, int64_t q0b, int64_t q0e, int accumulate, double* b,
+                    void* stream);
+/* acc[0] += sum_q w0 w1 w2 (u_h(q) - u[q0 - q0b, q1, q2])^2 over the range, u_h as
+ * poms_field_eval forms it; u NULL: the squared norm of u_h.  acc: one DEVICE double.
+ * The point values are not stored; per-thread chains stay under 4096 terms and the
+ * per-block sums are reduced by one block, deterministically.  Needs weights.         */
+int poms_field_error(poms_field* field, const double* x, const int* der, const double* u, int64_t q0b,
+                     int64_t q0e, double* acc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ __all__ = [
     "assemble_1d", "make_open_knots", "uniform_knots", "matrix_multi_stages",
     "pcg_glt", "pcg_kron", "KronSolver", "kron_solve_serial", "kron_solve_par", "to_bnd",
     "collocation_cardinal_splines", "MultilevelVCycle", "crl", "assemble_stencil",
+    "QuadGrid", "PointGrid", "assemble_rhs", "evaluate", "l2_error",
 ]
 
 
@@ -31,6 +32,9 @@ def __getattr__(name):
     if name == "assemble_stencil":
         from .assembly import assemble_stencil
         return assemble_stencil
+    if name in ("QuadGrid", "PointGrid", "assemble_rhs", "evaluate", "l2_error"):
+        from . import field
+        return getattr(field, name)
     if name in ("KronSolver", "kron_solve_serial", "kron_solve_par", "to_bnd"):
         from . import kron_solve
         return getattr(kron_solve, name)

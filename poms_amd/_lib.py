@@ -157,6 +157,11 @@ _SIGS = {
     "poms_op_timing_read": [_vp, _i, C.POINTER(_d), C.POINTER(_i64), C.POINTER(_i64)],
     "poms_kron_solve_bnd_3d": [_vp, _vp, _i64, _i, _i, _vp, _i64, _i, _i, _vp, _i64, _i, _i, _vp, _vp, _vp,
                                _vp],
+    "poms_field_create": [_vp, _i, _LP, C.POINTER(_i64), C.POINTER(_i), _vp, _vp, _vp, _vp, _vp, _i64, _pp],
+    "poms_field_destroy": [_vp],
+    "poms_field_eval": [_vp, _vp, C.POINTER(_i), _i64, _i64, _vp, _vp],
+    "poms_field_load": [_vp, _vp, _i64, _i64, _i, _vp, _vp],
+    "poms_field_error": [_vp, _vp, C.POINTER(_i), _vp, _i64, _i64, _vp, _vp],
 }
 _RESTYPES = {"poms_last_error": C.c_char_p}
 

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .splines import basis_funs_ders
+from .splines import basis_funs_ders, find_span
 from .stencil import StencilMatrix, StencilVectorSpace
 
 
@@ -57,6 +57,57 @@ def axis_tables(T: np.ndarray, p: int, nquad: int | None = None) -> dict:
             es[i] = min(es[i], e)
             ee[i] = max(ee[i], e)
     return dict(n=n, p=p, nel=nel, nq=nq, first=first, es=es, ee=ee, basis=basis, weights=weights, points=points)
+
+
+def point_tables(T: np.ndarray, p: int, pts) -> dict:
+    """1D tables of the B-splines at arbitrary points: ``pts`` is a non-decreasing
+    array in ``[T[p], T[n]]`` (repeats allowed).  ``first[q] = find_span - p`` is the
+    first non-zero basis function at point ``q`` (the right end point falls in the
+    last non-empty span, as :func:`find_span` puts it) and ``basis[q, a, 0:2]`` the
+    value and first derivative of function ``first[q] + a``."""
+    T = np.asarray(T, dtype=np.float64)
+    pts = np.atleast_1d(np.asarray(pts, dtype=np.float64))
+    n = len(T) - p - 1
+    if pts.ndim != 1 or pts.size < 1:
+        raise ValueError("points must be a non-empty 1D array")
+    if np.any(np.diff(pts) < 0):
+        raise ValueError("points must be non-decreasing")
+    if pts[0] < T[p] or pts[-1] > T[n]:
+        raise ValueError(f"points outside the domain [{T[p]}, {T[n]}]")
+    Q = pts.size
+    first = np.zeros(Q, dtype=np.int32)
+    basis = np.zeros((Q, p + 1, 2))
+    for q, x in enumerate(pts):
+        s = find_span(T, p, x)
+        first[q] = s - p
+        D = basis_funs_ders(T, p, x, s, 1)
+        basis[q, :, 0] = D[0]
+        basis[q, :, 1] = D[1]
+    return dict(n=n, p=p, Q=Q, points=pts.copy(), weights=None, first=first, basis=basis)
+
+
+def support_ranges(first: np.ndarray, p: int, n: int):
+    """Per basis function ``i`` the contiguous range ``[qlo[i], qhi[i])`` of the points
+    ``q`` with ``first[q] <= i <= first[q] + p`` (``first`` non-decreasing); empty
+    ranges have ``qlo == qhi``."""
+    first = np.asarray(first, dtype=np.int64)
+    i = np.arange(n)
+    qlo = np.searchsorted(first, i - p, side="left").astype(np.int32)
+    qhi = np.searchsorted(first, i, side="right").astype(np.int32)
+    return qlo, np.maximum(qhi, qlo)
+
+
+def quad_point_tables(T: np.ndarray, p: int, nquad: int | None = None) -> dict:
+    """:func:`axis_tables` flattened to one row per quadrature point (``Q = nel nq``
+    points in element order), with the support ranges the gather-form load vector
+    needs: basis function ``i`` is non-zero exactly at points ``qlo[i] .. qhi[i]-1``."""
+    t = axis_tables(T, p, nquad)
+    Q = t["nel"] * t["nq"]
+    first = np.repeat(t["first"], t["nq"]).astype(np.int32)
+    qlo, qhi = support_ranges(first, p, t["n"])
+    return dict(n=t["n"], p=p, Q=Q, nel=t["nel"], nq=t["nq"], points=t["points"].reshape(Q).copy(),
+                weights=t["weights"].reshape(Q).copy(), first=first,
+                basis=t["basis"].reshape(Q, p + 1, 2).copy(), qlo=qlo, qhi=qhi)
 
 
 def _coef_field(f, tabs, device):

@@ -268,6 +268,10 @@ struct poms_ksolve {
     BandLU f[3]{};
 };
 
+namespace poms {
+int ctx_device(const poms_ctx* ctx) { return ctx->device; }   // for the sources that see poms_ctx opaque
+}
+
 static hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 static bool layout_ok(const poms_layout* L) {
