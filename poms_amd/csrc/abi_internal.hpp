@@ -1,0 +1,222 @@
+// The handle types behind include/poms_hip.h and the few internals that cross the
+// files of the extern "C" boundary (abi_op.hip, abi_vec.hip, abi_transfer.hip,
+// abi_ksolve.hip, pcg_native.hip; comm.hip and spline_field.hip take declarations only).
+// A source that includes this header also names the three headers below itself:
+// build.py's dependency scan reads a source's own quoted includes only.
+#pragma once
+#include "common.hpp"
+#include "launchers.hpp"
+#include "split_hooks.hpp"
+#include "../../include/poms_hip.h"
+
+#include <algorithm>
+#include <vector>
+
+struct poms_ctx {
+    int device = 0;
+    double* scratch = nullptr;  // reduction partials
+};
+
+// Host-reduced partials of one speculative launch: blocks n at offset off of the pinned
+// region, kind bit 0 norm / bit 1 dot, into value index vi (+1 when both).
+struct SpecPart { int64_t off; int n; int kind; int vi; };
+
+// Created, configured and destroyed by abi_op.hip; the groups below say which file
+// writes what after creation.
+struct poms_op {
+    // ---- operator launch state (abi_op.hip; set at creation or by its setters) ----
+    poms_ctx* ctx = nullptr;
+    int ndim = 3, form = poms::FORM_SUM, pmax = 1, chunk = 0, tout = 0;
+    poms_layout L{};
+    int64_t g0 = 0, n0g = 1;
+    double *a0t = nullptr, *b0t = nullptr, *a1 = nullptr, *b1 = nullptr, *a2 = nullptr, *b2 = nullptr;
+    double *dg2a = nullptr, *dg2b = nullptr;  // contiguous axis-2 band diagonals
+    double* rdiag0 = nullptr;                  // 1/diag(A) per global plane (Toeplitz interior of axes 1, 2)
+    int variant = 0;
+    int last_variant = -1;    // the kernel variant the last operator launch ran (after per-call fall-backs)
+    bool v2_ok = false;       // storage pads == pmax on every used axis (the Toeplitz kernels' precondition)
+    bool ghost_corners = false;   // ghost edges / corners of axes 1 and 2 may be non-zero (a Cart block)
+    poms::ToepConst tc{};
+    double* coef = nullptr;   // FORM_STENCIL: (2p+1)^d coefficient planes of the owned rows
+    int sp[3]{};              // FORM_STENCIL: stencil half-widths per axis
+    uint64_t gen = 0;   // bumped by every setter that changes the launches a graph would capture
+    // op_run_split's interior launch: the communication stream's exchange and boundary
+    // launch run beside it (the automatic chunking leaves them CUs, op_geom); written
+    // by op_run_split only
+    bool split_interior = false;
+
+    // ---- partials routing (read by abi_op.hip's op_run / op_run_j2) ----
+    // where a launch writes its per-block partials: norms at scratch + part_off, dots
+    // at scratch + (dot_base < 0 ? nblk : dot_base) + part_off (op_run_split puts two
+    // launches' partials side by side and reduces them once); written by op_run_split only
+    int64_t part_off = 0, dot_base = -1;
+    // op_run: write the partials to part_dst instead of the scratch when they fit
+    // in part_cap doubles (last_part_host says whether they went there).  part_dst and
+    // part_cap are written by pcg_native.hip only, around one launch; last_part_host by
+    // op_run / op_run_j2
+    double* part_dst = nullptr;
+    int64_t part_cap = 0;
+    bool last_part_host = false;
+    // blocks of the last launch's partials (op_run, stencil_run, poms_op_diag_scale;
+    // pcg_native.hip's diag_scale_norm writes it too)
+    int64_t last_partials = 0;
+
+    // ---- native pcg slots (pcg_native.hip only; freed by poms_op_destroy) ----
+    // native pcg loop (poms_pcg_jacobi): device scalars and the pinned host slots
+    double* sv_dev = nullptr;
+    double* sv_host = nullptr;
+    // poms_pcg_jacobi, one rank: ring of pinned host slots the reduction kernels
+    // write the host-read norms into.  sv_seq[i] = launch sequence number that armed
+    // slot i (-1: never); every launch numbered below sv_done is known complete (a
+    // value written by a later launch of the same stream has been read), so its slot
+    // can be re-armed without a stale write landing after the sentinel.
+    static constexpr int kSvRing = 48;
+    int sv_next = 0;
+    int64_t sv_seq_next = 0, sv_done = 0;
+    int64_t sv_seq[kSvRing];
+    // ... and per slot a region of kSvPart doubles the operator launch writes its
+    // per-block partial sums into (no reduction launch: the host adds them in the
+    // reduction kernel's order when it reads the slot).  sv_npart[i] = blocks of the
+    // launch that last used region i (0: none pending), sv_pkind[i] bit 0 norm
+    // partials at [0, n), bit 1 dot partials after them.
+    static constexpr int kSvPart = 4096;
+    double* sv_part = nullptr;   // kSvRing x kSvPart, pinned, device-mapped, armed unset
+    int sv_npart[kSvRing] = {};
+    int sv_pkind[kSvRing] = {};
+    double* la_buf = nullptr;   // the two-sweep lookahead's fourth preconditioner buffer (zero ghosts)
+    double* la_raw = nullptr;   // its allocation: la_buf sits la_off doubles in, on the work vectors' 128-B phase
+    int64_t la_off = -1;
+    int64_t la_n = 0;
+
+    // ---- speculative / graph state (pcg_native.hip only; poms_op_spec_stats reads the
+    // counters, poms_op_destroy frees) ----
+    // poms_pcg_jacobi, speculative mode: the sweeps' per-block partials (pinned,
+    // device-mapped; kSpecPart doubles), the device array of the other host-read sums,
+    // and the backup of x0
+    static constexpr int64_t kSpecPart = 1 << 19;
+    static constexpr int kSpecVals = 4096;
+    double* spec_part = nullptr;
+    double* spec_dev = nullptr;
+    double* spec_host = nullptr;    // kSpecVals, pinned
+    double* spec_bak = nullptr;
+    int64_t spec_bak_n = 0;
+    struct SpecGraph {   // a captured speculative call (see pcg_speculative)
+        uint64_t key[16] = {};
+        hipGraphExec_t exec = nullptr;
+        std::vector<SpecPart> parts;
+        std::vector<int> chk, rr;
+        int sn = 0, vrr0 = 0;
+        int64_t use = 0;
+    };
+    static constexpr int kSpecGraphs = 4;
+    SpecGraph spec_graphs[kSpecGraphs];
+    int64_t spec_graph_clock = 0;
+    int spec_graph_hits = 0, spec_graph_caps = 0;   // graphs stop when captures outnumber hits
+    int spec_calls = 0, spec_repeats = 0;            // speculative calls, and those repeated step by step
+    hipStream_t cap_stream = nullptr;                 // private non-blocking capture stream
+
+    // ---- launch timing (abi_op.hip only: poms_op_timing, op_run) ----
+    // HIP events around every operator launch
+    struct TimedLaunch { int epi; int64_t ndof; hipEvent_t e0, e1; };
+    bool timing = false;
+    int t_epi = -1, t_every = 1;   // record launches of this epilogue only (-1: all), every n-th
+    int64_t t_seen = 0;
+    std::vector<TimedLaunch> tl;
+    size_t tl_used = 0;
+};
+
+// abi_transfer.hip only
+struct poms_transfer {
+    poms_ctx* ctx = nullptr;
+    int ndim = 3, ncm = 16;
+    poms_layout L{};
+    int64_t g0 = 0;
+    int64_t nf[3]{}, nc[3]{};
+    double* Pm[3]{};
+    // banded form (coarse extent > 32): rows of P (Pb, jlo, wP) and of P^T (Rb, ilo, wR)
+    bool banded = false;
+    double *Pb[3]{}, *Rb[3]{};
+    int *jlo[3]{}, *ilo[3]{};
+    int wP[3]{}, wR[3]{};
+    double *t0 = nullptr, *t1 = nullptr;
+    double* part = nullptr;   // split-axis restriction partials (few lines)
+    int64_t part_n = 0;
+    // fused residual -> restriction: planned by poms_transfer_set_operator, which owns
+    // every allocation below; poms_resid_restrict only launches
+    int rform = -1;           // POMS_FORM_SUM / POMS_FORM_SINGLE; -1: no operator set
+    int ncf = 0;              // columns of the fused passes' matrices (8, 12, 16, 32)
+    double* Gf[6]{};          // F^T P per operator role (last axis negated), ncf columns
+    double* Pf[3]{};          // P, ncf columns
+    double* ru = nullptr;     // axis-0 outputs: 3 x [c0][n1][n2]
+    double* rv = nullptr;     // axis-1 outputs: 3 x [c0][c1][n2]
+    // the call's passes in launch order (3D: axis 0, 1, 2; 2D: axis 1, 2): geometry,
+    // matrices and the ru / rv slices; x, b and the coarse output are null until a call
+    // fills its copy in
+    poms::MultiPass rpass[3]{};
+    int nrpass = 0;
+    double* mpart = nullptr;  // chunk partials of the fused passes: the largest pass's need
+    int64_t mpart_n = 0;
+};
+
+// abi_ksolve.hip only
+struct poms_ksolve {
+    poms_ctx* ctx = nullptr;
+    int ndim = 3;
+    poms_layout L{};
+    int64_t n0g = 1;
+    int64_t ng[3]{1, 1, 1};     // global extent of every axis (the factor sizes)
+    int info[3]{};
+    int kl[3]{}, ku[3]{};
+    std::vector<int> ipiv[3];   // absolute 0-based pivot rows (host copy, for callers)
+    double *Ld[3]{}, *Ud[3]{};
+    int* pivd[3]{};
+    poms::BandLU f[3]{};
+};
+
+inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+inline bool layout_ok(const poms_layout* L) {
+    if (!L) return false;
+    for (int d = 0; d < 3; ++d)
+        if (L->n[d] < 1 || L->pads[d] < 0) return false;
+    return L->pitch == 0 || L->pitch >= L->n[2] + 2 * L->pads[2];
+}
+
+inline poms::RowGeom row_geom(const poms_layout* L) {
+    poms::RowGeom g;
+    const int64_t c2 = L->pitch > 0 ? L->pitch : L->n[2] + 2 * L->pads[2];
+    const int64_t c1 = L->n[1] + 2 * L->pads[1];
+    g.s1 = c2;
+    g.s0 = c1 * c2;
+    g.n0 = (int)L->n[0];
+    g.n1 = (int)L->n[1];
+    g.n2 = (int)L->n[2];
+    g.pd0 = (int)L->pads[0];
+    g.pd1 = (int)L->pads[1];
+    g.pd2 = (int)L->pads[2];
+    return g;
+}
+
+inline int upload(const double* host, size_t n, double** dev) {
+    POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(dev), std::max<size_t>(n, 1) * sizeof(double)));
+    if (n) POMS_HIP_CHECK(hipMemcpy(*dev, host, n * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+}
+
+namespace poms {
+
+// abi_op.hip
+bool error_is_set();                         // a message is waiting in poms_last_error
+int ctx_device(const poms_ctx* ctx);         // for the sources that see poms_ctx opaque
+bool sweep2_ok(const poms_op* o);
+int op_run_epi(poms_op* op, int epilogue, double omega, const double* x, double* y, const double* b,
+               int64_t zb, int64_t ze, int64_t zb2, int64_t ze2, bool wn, bool wd, void* stream);
+int op_run_split(poms_op* op, int epilogue, double omega, const double* x, double* y, const double* b,
+                 int64_t ib, int64_t ie, int64_t b1s, int64_t b1e, int64_t b2s, int64_t b2e, double* norm_out,
+                 double* dot_out, const SplitHooks& h, void* stream);
+
+// abi_vec.hip
+int vec_copy_dot(poms_ctx* ctx, const poms_layout* L, const double* x, double* z, double* out_dev,
+                 void* stream);
+
+}  // namespace poms

@@ -12,7 +12,9 @@
 // per direction, `pyccel/kron_product.py:21-41`) and `comm.allreduce` of the
 // solver scalars (`sources/solvers.py:87-124`, `sources/mg_jac.py:95`).
 #include "common.hpp"
+#include "launchers.hpp"   // (through abi_internal.hpp; named for the build's dependency scan)
 #include "split_hooks.hpp"
+#include "abi_internal.hpp"
 #include "peer.hpp"
 #include "../../include/poms_hip.h"
 
@@ -136,12 +138,6 @@ static int refuse_in_capture(hipStream_t s, const char* what) {
         return 1;
     }
     return 0;
-}
-
-namespace poms {
-int op_run_split(poms_op* op, int epilogue, double omega, const double* x, double* y, const double* b,
-                 int64_t ib, int64_t ie, int64_t b1s, int64_t b1e, int64_t b2s, int64_t b2e, double* norm_out,
-                 double* dot_out, const SplitHooks& h, void* stream);
 }
 
 static bool getenv_off(const char* name) {

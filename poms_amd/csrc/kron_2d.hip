@@ -34,6 +34,7 @@
 // Preconditions (host): storage pads == P, one rank (zero ghost rows and columns),
 // array < 2 GiB.
 #include "common.hpp"
+#include "launchers.hpp"
 
 #include <cstdio>
 #include <cstdlib>

@@ -17,6 +17,7 @@
 //     memory operations: exact vmcnt counting).
 // Preconditions: storage pads == P on every used axis (checked by the host).
 #include "common.hpp"
+#include "launchers.hpp"
 
 #include <cstdlib>
 #include <type_traits>

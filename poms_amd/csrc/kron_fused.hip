@@ -26,6 +26,7 @@
 //     oldest slot completes one output plane per input plane.
 // No MFMA: 49 FMA per DOF at p=3 against 16 B/DOF of HBM traffic.
 #include "common.hpp"
+#include "launchers.hpp"
 
 namespace poms {
 

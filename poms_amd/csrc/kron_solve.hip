@@ -23,6 +23,7 @@
 //    forward and backward sweeps are separate launches (the backward re-reads
 //    the forward's output written by other lanes).
 #include "common.hpp"
+#include "launchers.hpp"
 
 #include <algorithm>
 #include <cmath>

@@ -23,6 +23,7 @@
 //     in a P+1 deep register history of the lane's centre tap.
 // Preconditions (checked by the host): storage pads == P on every used axis.
 #include "common.hpp"
+#include "launchers.hpp"
 
 namespace poms {
 

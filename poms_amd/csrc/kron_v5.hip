@@ -37,6 +37,7 @@
 // array < 2 GiB, and no odd P on layouts with data in the corner ghosts (the x-row
 // DMA pair holding storage column 0 of storage row 0 fails the range check there).
 #include "common.hpp"
+#include "launchers.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -1025,8 +1026,6 @@ void kron_v5_tile(int pmax, bool aligned, int* H, int* TO) {
 // slow paths.  Built once per geometry and device, outside any graph capture (a
 // launch during a capture that has no table yet keeps the default order).
 // POMS_V5_SCHED=0 turns it off.
-int kron_v5_rows(int pmax, int epi, int same12);
-
 static std::atomic<int> g_v5_sched{-1};
 
 int kron_v5_set_sched(int mode) {   // poms_diag_v5_sched

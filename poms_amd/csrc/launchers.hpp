@@ -1,0 +1,91 @@
+// Host-side launchers of the kernel files, declared once: every file that defines one
+// and every file that calls one includes this header (default arguments live here only).
+#pragma once
+#include "common.hpp"
+
+#include <vector>
+
+namespace poms {
+
+// ---- kron_fused.hip (v0), kron_dpp.hip (v3), kron_v4.hip, kron_v5.hip, kron_2d.hip ----
+int kron_launch(int pmax, bool is3d, int form, int epi, const KronPtrs& p, const KronGeom& g,
+                double omega, hipStream_t st);
+int kron_tile_rows();
+int kron_tile_cols();
+int kron_v3_launch(int variant, int pmax, bool is3d, int form, int epi, const KronPtrs& p,
+                   const KronGeom& g, const ToepConst& tc, double omega, hipStream_t st);
+int kron_v3_rows_2d();
+int kron_v4_launch(int pmax, bool is3d, int form, int epi, const KronPtrs& p, const KronGeom& g,
+                   const ToepConst& tc, double omega, hipStream_t st, int diag_mode);
+int kron_v5_launch(int pmax, int epi, const KronPtrs& p, const KronGeom& g, const ToepConst& tc, int H,
+                   double omega, hipStream_t st, int diag_mode);
+void kron_v5_tile(int pmax, bool aligned, int* H, int* TO);
+int kron_v5_rows(int pmax, int epi, int same12);
+int kron_v5_stamps(unsigned long long* host, int64_t n);
+int kron_v5_set_sched(int mode);
+void kron_v5_set_launch_events(hipEvent_t e0, hipEvent_t e1);
+bool kron_v5_launch_events_used();
+int kron2d_j2_rows();
+int kron2d_j2_rows_default();
+int kron2d_j2_cols(int pmax);
+int kron2d_j2_launch(int pmax, int form, const KronPtrs& p, const KronGeom& g, const ToepConst& tc, double omega,
+                     hipStream_t st, bool from_zero, double* part0);
+
+// ---- vec_ops.hip ------------------------------------------------------------------
+enum VecOp : int { V_AXPBY = 0, V_SCALE = 1, V_FILL = 2, V_DOT = 3, V_PCGUPD = 4, V_RUPD = 5, V_XPUPD = 6,
+                  V_SCALEDOT = 7 /* z = a x and z.z (flat kernel only) */,
+                  V_FINUPD = 8 /* pcg's last iteration, see stop_update */ };
+
+int vec_launch(int op, const RowGeom& g, double a, double b, const double* x, const double* y,
+               double* z, double* w, const double* q, double* partial, hipStream_t st,
+               int* nblk_out, const double* ab = nullptr);
+int vec_flat_launch(int op, int64_t count, double a, double b, const double* x, const double* y,
+                    double* z, double* w, const double* q, double* partial, hipStream_t st,
+                    int* nblk_out, const double* ab = nullptr, const AlphaFold* af = nullptr);
+int zero_ghosts_launch(const RowGeom& g, double* z, hipStream_t st);
+int reduce_launch(const double* partial, int count, double* out, hipStream_t st, int accumulate = 0);
+int reduce_wide_launch(const double* partial, int count, double* out, hipStream_t st, int accumulate = 0);
+int diag_scale_blocks(bool is3d, const RowGeom& g);
+int diag_scale_launch(bool is3d, int form, const RowGeom& g, int P, int g0, double scale,
+                      const double* b, double* x, const double* a0t, const double* b0t,
+                      const double* a1, const double* b1, const double* a2, const double* b2,
+                      double* partial, hipStream_t st, int* nblk_out);
+int dense_matvec_launch(int n, const double* M, const double* x, double* y, hipStream_t st);
+
+// ---- stencil_general.hip ----------------------------------------------------------
+int assemble_launch(const AssembleAxis* ax, int g0, int nl0, const double* a_q, const double* c_q, double mass_coef,
+                    double* coef, hipStream_t st);
+int stencil_to_spl_launch(const StencilGeom& g, const double* coef, double* out, hipStream_t st);
+int stencil_launch(int epi, const StencilGeom& g, const double* coef, const double* x, double* y,
+                   const double* b, double omega, double* partial, double* partial2, int max_blocks,
+                   hipStream_t st, int* nblk_out);
+
+// ---- transfer.hip -----------------------------------------------------------------
+int transfer_pass_launch(bool restrict_dir, int ncm, const AxisPass& ps, const double* Pm,
+                         const double* in, double* out, hipStream_t st, double* part);
+int transfer_split_scratch(int ncm, const AxisPass& ps);
+int transfer_band_launch(bool restrict_dir, const AxisPass& ps, const double* band, const int* lo, int w,
+                         const double* in, double* out, hipStream_t st);
+
+// One pass of the fused residual -> restriction: up to 3 inputs and 3 outputs
+// sharing one AxisPass geometry; m[o][k] (device, rows padded to the pass's ncm
+// columns, null = no term) maps input k into output o.
+struct MultiPass {
+    AxisPass ps;
+    const double* in[3];
+    double* out[3];
+    const double* m[3][3];
+    int ni, no;
+};
+
+int mrestrict_launch(int ncm, const MultiPass& mp, double* part, hipStream_t st);
+int64_t mrestrict_scratch(const MultiPass& mp, int ncm);
+
+// ---- kron_solve.hip ---------------------------------------------------------------
+int ksolve_strided_launch(const LineGeom& g, const BandLU& f, const double* in, double* out, hipStream_t st);
+int ksolve_rows_launch(const RowLines& g, const BandLU& f, const double* in, double* out, hipStream_t st);
+int band_lu(int64_t n, int kl, int ku, double* ab, int64_t ldab, int* ipiv);
+void band_lu_tables(int64_t n, int kl, int ku, const double* ab, int64_t ldab, const int* ipiv,
+                    std::vector<double>& L, std::vector<double>& U, std::vector<int>& piv);
+
+}  // namespace poms

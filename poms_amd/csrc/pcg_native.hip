@@ -1,0 +1,1056 @@
+// extern "C" boundary of libpoms_hip.so (declared in include/poms_hip.h):
+// poms_pcg_jacobi, the native pcg + damped-Jacobi loop with its scalar kernels and its
+// opt-in speculative and graph modes.
+#include "common.hpp"
+#include "launchers.hpp"
+#include "split_hooks.hpp"
+#include "abi_internal.hpp"
+#include "../../include/poms_hip.h"
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+using namespace poms;
+
+// ---- native pcg + damped-Jacobi loop (poms_pcg_jacobi) ------------------------
+// The V-cycle's smoother (`sources/mg_jac.py:88,104` -> `sources/solvers.py:69-135`
+// with psolve = damped_jacobi, :167-235) as one C call: the same launches, device
+// scalars and stop tests as poms_amd.solvers._pcg_device, without a Python round
+// trip per launch.  The host reads a norm one launch after queuing the next one
+// (the GPU never waits for the host while the host waits for that norm).
+namespace {
+
+// device scalars (the sums only the host reads live in host slots / comm ring slots)
+enum { SC_SR = 0, SC_PQ = 1, SC_ONE = 2, SC_ALPHA = 3, SC_ALPHA2 = 4, SC_BETA = 5, SC_SRN = 6, SC_N = 16 };
+enum { H_RR0 = 0, H_RR = 1, H_J0 = 2 /* 2 slots */, H_JN = 4 /* 2 slots */ };
+// an unwritten partial in a host region: a NaN payload no reduction produces
+constexpr uint64_t kPartUnset = 0x7ff8dead0000beefull;
+
+__global__ void pcg_scalars_kernel(double* sc, int mode) {
+    if (threadIdx.x != 0) return;
+    if (mode == 0) {            // alpha = s.r / p.q; pairs [1, alpha] and [alpha, beta]
+        const double a = sc[SC_SR] / sc[SC_PQ];
+        sc[SC_ONE] = 1.0;
+        sc[SC_ALPHA] = a;
+        sc[SC_ALPHA2] = a;
+    } else {                    // beta = s.r / s.r_old; s.r_old <- s.r
+        sc[SC_BETA] = sc[SC_SRN] / sc[SC_SR];
+        sc[SC_SR] = sc[SC_SRN];
+    }
+}
+
+// p.q from the apply + dot launch's per-block partials -- reduce_partials_kernel's
+// order, so the same bits -- and alpha from it, in one launch (one rank: saves the
+// one-block reduction launch per pcg iteration)
+__global__ void __launch_bounds__(256) pcg_alpha_kernel(const double* __restrict__ part, int count, double* sc) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < count; i += 256) s += part[i];
+    const double pq = block_sum_256(s, red);
+    if (threadIdx.x != 0) return;
+    sc[SC_PQ] = pq;
+    const double a = sc[SC_SR] / pq;
+    sc[SC_ONE] = 1.0;
+    sc[SC_ALPHA] = a;
+    sc[SC_ALPHA2] = a;
+}
+
+// s.r_new from the last damped-Jacobi sweep's per-block partials (reduce_partials_kernel's
+// order: the same bits), then beta = s.r_new / s.r_old and s.r_old <- s.r_new, in one
+// launch (one rank: saves the one-block reduction launch per pcg iteration)
+// s.r_old <- s.r_new, where a beta folded into the x/p update left it pending and no
+// folded r update follows (AlphaFold)
+__global__ void pcg_sr_fix_kernel(double* sc) {
+    if (threadIdx.x == 0) sc[SC_SR] = sc[SC_SRN];
+}
+
+__global__ void __launch_bounds__(256) pcg_beta_kernel(const double* __restrict__ part, int count, double* sc) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < count; i += 256) s += part[i];
+    const double srn = block_sum_256(s, red);
+    if (threadIdx.x != 0) return;
+    sc[SC_SRN] = srn;
+    sc[SC_BETA] = srn / sc[SC_SR];
+    sc[SC_SR] = srn;
+}
+
+struct PcgRun {
+    poms_op* op;
+    poms_comm* comm;
+    const poms_pcg_opts* o;
+    hipStream_t st;
+    void* stv;
+    double* sc;
+    double* host;
+    int64_t n0 = 1;
+
+    int run(int epi, const double* x, double* y, const double* b, double* nrm, double* dot) {
+        if (comm) {
+            const RowGeom g = row_geom(&op->L);
+            int tk = -1;
+            return poms_op_run_dist(op, comm, epi, o->omega, x, y, b, const_cast<double*>(x), g.s0, op->L.n[0],
+                                    (int)op->L.pads[0], op->pmax, o->prev, o->next, 1, nrm ? 1 : 0, dot ? 1 : 0, nrm,
+                                    dot, 0, nullptr, &tk, stv);
+        }
+        return poms_op_run_reduce2(op, epi, o->omega, x, y, b, 0, n0, 0, 0, nrm, dot, 0, stv);
+    }
+    // q = A p, p.q and alpha: one rank folds p.q's reduction into the alpha kernel
+    int apd_alpha(const double* p, double* q) {
+        if (comm || op->dot_base >= 0 || op->part_off != 0 || op->part_dst || op->form == FORM_STENCIL) {
+            if (run(EPI_APPLYDOT, p, q, p, nullptr, sc + SC_PQ) || allsum(sc + SC_PQ, 1)) return 1;
+            hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, st, sc, 0);
+            POMS_HIP_CHECK(hipGetLastError());
+            return 0;
+        }
+        if (op_run_epi(op, EPI_APPLYDOT, o->omega, p, q, p, 0, n0, 0, 0, false, true, stv)) return 1;
+        const int64_t n = op->last_partials;   // (the dot's partials at scratch + n, as poms_op_run_reduce2 reads them)
+        // alpha is formed by the r update that follows (rupd: AlphaFold), or by
+        // pcg_alpha_kernel when that cannot take it (flush_alpha)
+        alpha_part = op->ctx->scratch + n;
+        alpha_n = n;
+        return 0;
+    }
+    const double* alpha_part = nullptr;   // p.q's partials awaiting alpha (apd_alpha)
+    int64_t alpha_n = 0;
+    bool sr_stale = false;                // a folded beta left s.r_old <- s.r_new pending
+    int fix_sr() {
+        if (!sr_stale) return 0;
+        hipLaunchKernelGGL(pcg_sr_fix_kernel, dim3(1), dim3(64), 0, st, sc);
+        sr_stale = false;
+        POMS_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    static bool fold_on() {   // POMS_ALPHA_FOLD=0: the one-block scalar kernels (tuning / A-B)
+        static const bool f = !(getenv("POMS_ALPHA_FOLD") && getenv("POMS_ALPHA_FOLD")[0] == '0');
+        return f;
+    }
+    // beta folded into the x/p update: x += alpha p, p = s + beta p with beta from the
+    // last sweep's x . rhs partials (dot_part); 1 if it cannot (the caller runs
+    // pcg_beta_kernel and the plain update), -1 on error
+    int xpupd_beta(double* x, double* p, const double* s) {
+        if (!fold_on() || !direct() || (op->L.flags & POMS_LAYOUT_GHOST_DATA) || dot_part_n < 0) return 1;
+        const RowGeom g = row_geom(&op->L);
+        const int64_t off = (int64_t)g.pd0 * g.s0, count = (int64_t)g.n0 * g.s0;
+        const int head = (reinterpret_cast<uintptr_t>(x + off) & 15) ? 1 : 0;
+        const int64_t nbp = std::max<int64_t>(1, ((count - head) / 2 + 1023) / 1024);
+        if (dot_part_n * nbp > (int64_t)1 << 20) return 1;
+        if (fix_sr()) return -1;   // (beta reads s.r_old at sc[SC_SR])
+        AlphaFold bf;
+        bf.part = dot_part;
+        bf.n = (int)dot_part_n;
+        bf.sc = sc;
+        static_assert(SC_SR == 0 && SC_BETA == 5 && SC_SRN == 6, "AlphaFold's beta slots");
+        int nb = 0;
+        if (vec_flat_launch(V_XPUPD, count, 0.0, 0.0, s + off, nullptr, x + off, p + off, nullptr, nullptr, st, &nb,
+                            sc + SC_ALPHA2, &bf) != 0)
+            return 1;
+        if (hipGetLastError() != hipSuccess) { set_error("x/p update with beta: launch failed"); return -1; }
+        sr_stale = true;
+        return 0;
+    }
+    int flush_alpha() {
+        if (fix_sr()) return 1;
+        if (!alpha_part) return 0;
+        hipLaunchKernelGGL(pcg_alpha_kernel, dim3(1), dim3(256), 0, st, alpha_part, (int)alpha_n, sc);
+        alpha_part = nullptr;
+        POMS_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    // the last sweep of a psolve left x . rhs as per-block partials (dot_part, dot_part_n
+    // blocks) for pcg_beta_kernel instead of reducing them itself (-1: it did not)
+    const double* dot_part = nullptr;
+    int64_t dot_part_n = -1;
+    int tk[poms_op::kSvRing] = {};   // with a communicator: the ring ticket of host slot h
+    // a sum the device needs (alpha, beta): all-reduced, the compute stream waits
+    int allsum(double* d, int cnt) { return comm ? poms_allreduce_sum(comm, d, cnt, stv, 1) : 0; }
+    // A value only the host reads: one rank -- the reduction kernel writes it straight
+    // into the pinned (coherent, device-mapped) host slot, armed with a sentinel the
+    // host spins on (~1-2 us after the kernel instead of an event wake-up, ~15 us:
+    // profiles/r02/sync_probe.log); with a communicator -- a ring slot of the
+    // communicator, all-reduced and copied to the host slot on the communication
+    // stream while the compute stream goes on (lazy_post; the compute stream used to
+    // wait for that all-reduce and copy, ~40 us per sweep in profiles/r03/proxy/).
+    bool direct() const { return comm == nullptr; }
+    double* hslot(int h) {
+        if (direct()) return host + h;
+        double* d = nullptr;
+        if (poms_comm_slot(comm, &d, &tk[h])) return nullptr;
+        return d;
+    }
+    int lazy_post(int h, int cnt) { return direct() ? 0 : poms_allreduce_to_host(comm, tk[h], cnt, host + h, stv); }
+    // an operator launch whose sums only the host reads: [dot, norm] from host slot h
+    int jrun(int epi, const double* x, double* y, const double* b, bool wn, bool wd, int h) {
+        if (direct()) {   // the launch writes its partials into slot h's host region
+            // (up to host_partials_max() blocks).  A/B on one box
+            // (profiles/r03/host_partials/): 2D 1027^2 cycle 4.5-5.2 -> 3.6-3.7 ms,
+            // 3D 515^3 195.0-195.5 -> 194.9-195.3 ms
+            op->part_dst = op->sv_part + (size_t)h * poms_op::kSvPart;
+            op->part_cap = ((wn ? 1 : 0) + (wd ? 1 : 0)) * host_partials_max();
+            const int rc = op_run_epi(op, epi, o->omega, x, y, b, 0, n0, 0, 0, wn, wd, stv);
+            op->part_dst = nullptr;
+            if (rc) return 1;
+            const int64_t n = op->last_partials;
+            if (op->last_part_host) {
+                op->sv_npart[h] = (int)n;
+                op->sv_pkind[h] = (wn ? 1 : 0) | (wd ? 2 : 0);
+                return 0;
+            }
+            // too many blocks for the region: reduce on the device into the slots
+            double* pdot = op->ctx->scratch + (op->dot_base < 0 ? n : op->dot_base);
+            if ((wn && reduce_launch(op->ctx->scratch, (int)n, host + h + (wd ? 1 : 0), st)) ||
+                (wd && reduce_launch(pdot, (int)n, host + h, st))) {
+                set_error("poms_pcg_jacobi: reduction launch failed");
+                return 1;
+            }
+            POMS_HIP_CHECK(hipGetLastError());
+            return 0;
+        }
+        const RowGeom g = row_geom(&op->L);
+        return poms_op_run_dist(op, comm, epi, o->omega, x, y, b, const_cast<double*>(x), g.s0, op->L.n[0],
+                                (int)op->L.pads[0], op->pmax, o->prev, o->next, 1, wn ? 1 : 0, wd ? 1 : 0, nullptr,
+                                nullptr, (wn ? 1 : 0) + (wd ? 1 : 0), host + h, &tk[h], stv);
+    }
+    // sweeps 1-3 from x = 0 (one rank): [||x1||^2, ||dr_2||^2, ||dr_3||^2] into slots h .. h+2
+    int jrun3(const double* rhs, double* y, int h) {
+        op->part_dst = op->sv_part + (size_t)h * poms_op::kSvPart;
+        op->part_cap = 3 * host_partials_max();
+        const int rc = op_run_epi(op, EPI_JACOBI3Z, o->omega, rhs, y, rhs, 0, n0, 0, 0, true, true, stv);
+        op->part_dst = nullptr;
+        if (rc) return 1;
+        const int64_t n = op->last_partials;
+        if (op->last_part_host) {
+            op->sv_npart[h] = (int)n;
+            op->sv_pkind[h] = 4;
+            return 0;
+        }
+        for (int i = 0; i < 3; ++i)
+            if (reduce_launch(op->ctx->scratch + i * n, (int)n, host + h + i, st)) {
+                set_error("poms_pcg_jacobi: reduction launch failed");
+                return 1;
+            }
+        POMS_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    // Arm `cnt` consecutive host slots for the next launch and return the first.
+    // Direct mode takes fresh slots from a ring: a launch the loop abandoned (an
+    // early damped-Jacobi stop leaves the next sweep queued) still writes ITS slot
+    // later, so a slot is re-armed only once that launch is known complete -- a value
+    // of a later launch has been read (launches of one stream finish in order) --
+    // else the stream is drained first (advisor finding, round 2).
+    int arm(int fixed_h, int cnt) {
+        if (!direct()) return fixed_h;
+        if (op->sv_next + cnt > poms_op::kSvRing) op->sv_next = 0;
+        const int h = op->sv_next;
+        op->sv_next += cnt;
+        for (int i = 0; i < cnt; ++i)
+            if (op->sv_seq[h + i] >= op->sv_done) {
+                (void)hipStreamSynchronize(st);
+                op->sv_done = op->sv_seq_next;
+                break;
+            }
+        for (int i = 0; i < cnt; ++i) {
+            reinterpret_cast<volatile double*>(host)[h + i] = -1.0;   // norms are >= 0
+            op->sv_seq[h + i] = op->sv_seq_next;
+            if (op->sv_npart[h + i] > 0) {   // an abandoned launch's partials (complete by now): re-arm
+                part_arm(op->sv_part + (size_t)(h + i) * poms_op::kSvPart, pk_nsum(op->sv_pkind[h + i]) * op->sv_npart[h + i]);
+                op->sv_npart[h + i] = 0;
+                op->sv_pkind[h + i] = 0;
+            }
+        }
+        ++op->sv_seq_next;
+        return h;
+    }
+    static int64_t host_partials_max() {   // tuning: POMS_HOST_PARTIALS (0: always reduce on the device)
+        // read per launch (a getenv against a kernel launch): the parity tests switch it
+        // inside one process to run the device-reduction fall-back
+        const char* e = getenv("POMS_HOST_PARTIALS");
+        const int64_t m = e ? std::max<int64_t>(0, atoll(e)) : poms_op::kSvPart / 2;
+        return std::min<int64_t>(m, poms_op::kSvPart / 2);
+    }
+    // Wait for every partial of slot h's region and add them on the host in the
+    // order of reduce_partials_kernel (256 strided running sums, the 64-lane xor
+    // butterfly, then (w0 + w1) + (w2 + w3)): the same bits as the device reduction.
+    static double host_reduce(const double* p, int n) {
+        double sv[256];
+        for (int t = 0; t < 256; ++t) {
+            double a = 0.0;
+            for (int i = t; i < n; i += 256) a += p[i];
+            sv[t] = a;
+        }
+        double red[4];
+        for (int w = 0; w < 4; ++w) {
+            double v[64], nv[64];
+            for (int l = 0; l < 64; ++l) v[l] = sv[64 * w + l];
+            for (int off = 32; off > 0; off >>= 1) {
+                for (int l = 0; l < 64; ++l) nv[l] = v[l] + v[l ^ off];
+                for (int l = 0; l < 64; ++l) v[l] = nv[l];
+            }
+            red[w] = v[0];
+        }
+        return (red[0] + red[1]) + (red[2] + red[3]);
+    }
+    int settle_partials(int h) {
+        const int n = op->sv_npart[h];
+        double* reg = op->sv_part + (size_t)h * poms_op::kSvPart;
+        const int nsum = pk_nsum(op->sv_pkind[h]);
+        for (int i = 0; i < nsum * n; ++i) {
+            for (long k = 1; part_unset(reg + i); ++k) {
+                __builtin_ia32_pause();
+                if ((k & 4095) == 0 && hipStreamQuery(st) != hipErrorNotReady) {
+                    std::atomic_thread_fence(std::memory_order_seq_cst);
+                    if (part_unset(reg + i)) return 1;   // never written: the launch failed
+                }
+            }
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+        const bool wn = op->sv_pkind[h] & 1, wd = op->sv_pkind[h] & 2;
+        if (op->sv_pkind[h] & 4) {   // three sums, slots h .. h+2 (EPI_JACOBI3Z)
+            for (int i = 0; i < 3; ++i) host[h + i] = host_reduce(reg + (size_t)i * n, n);
+        } else {
+            if (wn) host[h + (wd ? 1 : 0)] = host_reduce(reg, n);
+            if (wd) host[h] = host_reduce(reg + (wn ? n : 0), n);
+        }
+        part_arm(reg, nsum * n);
+        op->sv_npart[h] = 0;
+        op->sv_pkind[h] = 0;
+        return 0;
+    }
+    // sums in a slot region: bit 0 a norm, bit 1 a dot, bit 2 three sums (EPI_JACOBI3Z)
+    static int pk_nsum(int pk) { return (pk & 4) ? 3 : ((pk & 1) ? 1 : 0) + ((pk & 2) ? 1 : 0); }
+    static bool part_unset(const double* v) {
+        uint64_t u;
+        const volatile uint64_t* q = reinterpret_cast<const volatile uint64_t*>(v);
+        u = *q;
+        return u == kPartUnset;
+    }
+    static void part_arm(double* v, int n) {
+        volatile uint64_t* q = reinterpret_cast<volatile uint64_t*>(v);
+        for (int i = 0; i < n; ++i) q[i] = kPartUnset;
+    }
+    // A failed wait (the shm sum timed out, a launch never wrote its sum) sets
+    // `failed` and keeps poms_comm_wait's message: the loop returns 1 at its next
+    // check instead of carrying a NaN into the stop tests (advisor, round 3).
+    bool failed = false;
+    double fail() {
+        failed = true;
+        return std::nan("");
+    }
+    double get(int h, int i = 0) {
+        if (!direct()) {
+            if (poms_comm_wait(comm, tk[h])) return fail();
+            return host[h + i];
+        }
+        if (op->sv_npart[h] > 0) {
+            if (settle_partials(h)) {
+                set_error("poms_pcg_jacobi: a launch did not write its partial sums");
+                return fail();
+            }
+            op->sv_done = std::max(op->sv_done, op->sv_seq[h] + 1);
+            return host[h + i];
+        }
+        const volatile double* v = reinterpret_cast<const volatile double*>(host) + h + i;
+        for (long n = 1; *v == -1.0; ++n) {
+            __builtin_ia32_pause();
+            if ((n & 4095) == 0 && hipStreamQuery(st) != hipErrorNotReady) {   // stream drained (or failed)
+                std::atomic_thread_fence(std::memory_order_seq_cst);
+                if (*v == -1.0) {   // never written: the launch failed
+                    set_error("poms_pcg_jacobi: a launch did not write its sum");
+                    return fail();
+                }
+            }
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+        op->sv_done = std::max(op->sv_done, op->sv_seq[h + i] + 1);   // that launch and all before it are done
+        return *v;
+    }
+    int dot(const double* a, const double* b, double* dst) {
+        if (poms_vec_dot(op->ctx, &op->L, a, b, dst, stv)) return 1;
+        return allsum(dst, 1);
+    }
+    // r -= alpha q, r.r -> host slot h.  One rank: the flat kernel writes its per-block
+    // partials straight into the slot's host region (the host adds them in the order
+    // of the device reduction it replaces, so the same bits) -- one launch less per
+    // pcg iteration.
+    // With x and p (skip_tail's last iteration): the final pass instead -- x += alpha p as
+    // well, r - alpha q not kept (V_FINUPD); the same count, head, grid and per-thread
+    // order, so the partials and r.r are the r update's bits.
+    int rupd(double* r, const double* q, int h, double* x = nullptr, const double* p = nullptr) {
+        if (direct() && !(op->L.flags & POMS_LAYOUT_GHOST_DATA)) {
+            const RowGeom g = row_geom(&op->L);
+            const int64_t off = (int64_t)g.pd0 * g.s0, count = (int64_t)g.n0 * g.s0;
+            const int head = (reinterpret_cast<uintptr_t>(r + off) & 15) ? 1 : 0;
+            const int64_t nbp = std::max<int64_t>(1, ((count - head) / 2 + 1023) / 1024);   // (vec_flat_launch's grid, before its cap)
+            if (nbp <= host_partials_max()) {
+                int nb = 0;
+                double* reg = op->sv_part + (size_t)h * poms_op::kSvPart;
+                // alpha folded into this launch where its blocks' extra reads of the
+                // partials are small (2D: 468 partials x ~515 blocks; not the 3D grid's
+                // 495 x 65536): one launch less per pcg iteration (round 6)
+                AlphaFold af;
+                static const bool fold = !(getenv("POMS_ALPHA_FOLD") && getenv("POMS_ALPHA_FOLD")[0] == '0');
+                if (fold && alpha_part && alpha_n * nbp <= (int64_t)1 << 20) {
+                    af.part = alpha_part;
+                    af.n = (int)alpha_n;
+                    af.sc = sc;
+                    af.sr = sr_stale ? SC_SRN : SC_SR;   // (a folded beta's s.r_new, copied to SC_SR by block 0)
+                    af.copy_sr = sr_stale ? 1 : 0;
+                    static_assert(SC_SR == 0 && SC_PQ == 1 && SC_ONE == 2 && SC_ALPHA == 3 && SC_ALPHA2 == 4,
+                                  "AlphaFold's slots");
+                } else if (flush_alpha()) {
+                    return 1;
+                }
+                if (vec_flat_launch(x ? V_FINUPD : V_RUPD, count, 0.0, 0.0, nullptr, x ? p + off : nullptr,
+                                    x ? x + off : nullptr, r + off, q + off, reg, st, &nb, sc + SC_ALPHA,
+                                    af.part ? &af : nullptr) == 0) {
+                    if (af.part) sr_stale = false;
+                    alpha_part = nullptr;
+                    POMS_HIP_CHECK(hipGetLastError());
+                    op->sv_npart[h] = nb;
+                    op->sv_pkind[h] = 1;
+                    return 0;
+                }
+            }
+        }
+        if (flush_alpha()) return 1;
+        double* d = hslot(h);
+        if (!d) return 1;
+        if (x ? poms_pcg_final_update_dev(op->ctx, &op->L, sc + SC_ALPHA, x, p, r, q, d, stv)
+              : poms_pcg_r_update_dev(op->ctx, &op->L, sc + SC_ALPHA, r, q, d, stv))
+            return 1;
+        return lazy_post(h, 1);
+    }
+    int diag_scale_norm(const double* b, double* x, int h) {   // x = omega b / diag, ||x||^2 -> host slot h
+        if (direct() && op->form != FORM_STENCIL) {   // partials straight into slot h's host region
+            const RowGeom g = row_geom(&op->L);
+            const int nb = diag_scale_blocks(op->ndim == 3, g);
+            if (nb <= host_partials_max()) {
+                int nl = 0;
+                diag_scale_launch(op->ndim == 3, op->form, g, op->pmax, (int)op->g0, o->omega, b, x, op->a0t,
+                                  op->b0t, op->a1, op->b1, op->dg2a, op->dg2b,
+                                  op->sv_part + (size_t)h * poms_op::kSvPart, st, &nl);
+                POMS_HIP_CHECK(hipGetLastError());
+                if (nl != nb) { set_error("diag scale: block count mismatch"); return 1; }
+                op->last_partials = nb;
+                op->sv_npart[h] = nb;
+                op->sv_pkind[h] = 1;
+                return 0;
+            }
+        }
+        if (poms_op_diag_scale(op, o->omega, b, x, 1, stv)) return 1;
+        double* d = hslot(h);
+        if (!d) return 1;
+        reduce_launch(op->ctx->scratch, (int)op->last_partials, d, st);
+        return lazy_post(h, 1);
+    }
+
+    // ---- speculative mode (spec_*): the whole smoother call is queued without reading a
+    // single stop test; every host-read sum goes to its own place (a partials region of
+    // op->spec_part, or op->spec_dev[i]) and the tests are evaluated once the stream has
+    // drained.  If one of them fires, the call is repeated step by step (x0 restored).
+    // The launches and their order are those of the step-by-step loop when no test
+    // fires, so the result is the same bits (tests/test_gpu_solvers.py).
+    using SPart = SpecPart;
+    std::vector<SPart> sparts;
+    int64_t scur = 0;       // next free double of op->spec_part
+    int sn = 0;             // next free value index
+    std::vector<int> schk;  // value indices tested against jtol^2 (< fires)
+    std::vector<int> srr;   // pcg r.r value index per iteration (k = 1..)
+    int svals(int cnt) {
+        const int i = sn;
+        sn += cnt;
+        return i;
+    }
+    // an operator launch whose sums are tested at the end: [dot, norm] at value vi
+    int sjrun(int epi, const double* x, double* y, const double* b, bool wn, bool wd, int* vi_out) {
+        const int cnt = (wn ? 1 : 0) + (wd ? 1 : 0);
+        const int vi = svals(cnt);
+        *vi_out = vi;
+        double* dn = wn ? op->spec_dev + vi + (wd ? 1 : 0) : nullptr;
+        double* dd = wd ? op->spec_dev + vi : nullptr;
+        if (!direct()) return run(epi, x, y, b, dn, dd);
+        op->part_dst = op->spec_part + scur;
+        op->part_cap = poms_op::kSpecPart - scur;
+        const int rc = op_run_epi(op, epi, o->omega, x, y, b, 0, n0, 0, 0, wn, wd, stv);
+        op->part_dst = nullptr;
+        if (rc) return 1;
+        const int64_t n = op->last_partials;
+        if (op->last_part_host) {
+            sparts.push_back(SPart{scur, (int)n, (wn ? 1 : 0) | (wd ? 2 : 0), vi});
+            scur += cnt * n;
+            return 0;
+        }
+        double* pdot = op->ctx->scratch + (op->dot_base < 0 ? n : op->dot_base);
+        if (wn) reduce_launch(op->ctx->scratch, (int)n, dn, st);
+        if (wd) reduce_launch(pdot, (int)n, dd, st);
+        POMS_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    // damped_jacobi with every sweep queued (no stop test read); as damped_jacobi below
+    int spec_damped_jacobi(const double* rhs, double* A, double* B, int dot_idx, double** out) {
+        const int maxit = o->jmaxiter;
+        double *x = A, *xn = B;
+        int fz = 0, k0;
+        if (maxit >= 2 && maxit != 2 && op->form != FORM_STENCIL) (void)poms_op_from_zero_supported(op, &fz);
+        if (fz) {   // sweeps 1, 2 from x = 0: [||x1||^2, ||dr2||^2]
+            int vi;
+            if (sjrun(EPI_JACOBI0, rhs, A, rhs, true, true, &vi)) return 1;
+            schk.push_back(vi);
+            schk.push_back(vi + 1);
+            k0 = 3;
+        } else {
+            const int vi = svals(1);
+            if (poms_op_diag_scale(op, o->omega, rhs, A, 1, stv)) return 1;
+            reduce_launch(op->ctx->scratch, (int)op->last_partials, op->spec_dev + vi, st);   // (rank sums at the end)
+            schk.push_back(vi);
+            k0 = 2;
+        }
+        for (int k = k0; k <= maxit; ++k) {
+            if (k == maxit) {   // the last sweep's norm cannot change the result: x . rhs instead
+                if (run(EPI_JACOBI, x, xn, rhs, nullptr, sc + dot_idx) || allsum(sc + dot_idx, 1)) return 1;
+            } else {
+                int vi;
+                if (sjrun(EPI_JACOBI, x, xn, rhs, true, false, &vi)) return 1;
+                schk.push_back(vi);
+            }
+            std::swap(x, xn);
+        }
+        *out = x;
+        return 0;
+    }
+    // damped_jacobi(A, rhs) with x0 = None into buffers {A, B} (and C: see below); the
+    // last sweep also forms x . rhs into sc[dot_idx] (*dot_done = 1), else the caller
+    // forms it.  Each sweep's stop test is read after the next sweep is queued -- or,
+    // with a third buffer C (one rank), after the next TWO are queued: the sweeps rotate
+    // over three buffers, so the two queued past a stop that fires (abandoned) cannot
+    // overwrite the result, and the host's turn-around per sweep can take up to two
+    // sweeps' time before the GPU waits.  The same launches and bits either way.
+    int damped_jacobi(const double* rhs, double* A, double* B, int dot_idx, double** out, int* dot_done,
+                      double* C = nullptr) {
+        const double tol2 = o->jtol * o->jtol;
+        const int maxit = o->jmaxiter;
+        *dot_done = 0;
+        double* bufs[3] = {A, B, C};
+        const int nb = C ? 3 : 2, depth = C ? 2 : 1;
+        // two sweeps per launch (one rank, 2D p = 3, three buffers; POMS_J2=0: off):
+        // sweeps k, k+1 from bufs[cur] into bufs[nxt]; x_k is not stored
+        static const bool j2_env = !(getenv("POMS_J2") && getenv("POMS_J2")[0] == '0');
+        const bool j2 = j2_env && C && direct() && sweep2_ok(op);
+        int cur = 0;                              // buffer of the latest queued x
+        struct Pend { int kind, h, buf, in; };    // 1: sweep norm in slot h; 2: the from-zero
+        Pend q[2];                                // pair; 3: a two-sweep launch from bufs[in];
+                                                  // 5: sweeps 1-3 from zero
+        int nq = 0, ring = 0, k0;
+        int fz = 0;
+        if (maxit >= 2 && maxit != 2 && op->form != FORM_STENCIL) (void)poms_op_from_zero_supported(op, &fz);
+        // sweeps 1-3 from x = 0 in one launch where the two-sweep launches run (POMS_J2FZ=0: off)
+        static const bool j3_env = !(getenv("POMS_J2FZ") && getenv("POMS_J2FZ")[0] == '0');
+        if (fz && j2 && j3_env && maxit >= 4) {   // [||x1||^2, ||dr2||^2, ||dr3||^2]
+            const int h0 = arm(H_J0, 3);
+            if (jrun3(rhs, A, h0)) return 1;
+            q[nq++] = Pend{5, h0, 0, -1};
+            k0 = 4;
+        } else if (fz) {   // sweeps 1, 2 from x = 0 in one pass over rhs: [||x1||^2, ||dr2||^2]
+            const int h0 = arm(H_J0, 2);
+            if (jrun(EPI_JACOBI0, rhs, A, rhs, true, true, h0)) return 1;
+            q[nq++] = Pend{2, h0, 0, -1};
+            k0 = 3;
+        } else {
+            if (maxit < 1) { set_error("pcg: jacobi maxiter < 1"); return 1; }
+            const int h = arm(H_JN, 1);
+            if (diag_scale_norm(rhs, A, h)) return 1;
+            q[nq++] = Pend{1, h, 0, -1};
+            ring = 1;
+            k0 = 2;
+        }
+        // the oldest open stop test: done with *res when it fires
+        auto settle = [&](bool& done, double*& res) {
+            done = false;
+            const Pend f = q[0];
+            q[0] = q[1];
+            --nq;
+            if (f.kind == 2) {
+                if (get(f.h, 0) < tol2) {   // the reference stops after sweep 1: x1 itself
+                    // (into the buffer the abandoned sweep 3 wrote; queued after every sweep
+                    // that reads it)
+                    double* x1 = bufs[(f.buf + 1) % nb];
+                    if (poms_op_diag_scale(op, o->omega, rhs, x1, 0, stv)) return 1;
+                    done = true;
+                    res = x1;
+                } else if (get(f.h, 1) < tol2) {
+                    done = true;
+                    res = bufs[f.buf];
+                }
+            } else if (f.kind == 5) {   // sweeps 1-3 from zero; x1 and x2 re-formed into the
+                double* xr = bufs[(f.buf + 1) % nb];   // buffer the abandoned next launch wrote
+                if (get(f.h, 0) < tol2) {
+                    if (poms_op_diag_scale(op, o->omega, rhs, xr, 0, stv)) return 1;
+                    done = true;
+                    res = xr;
+                } else if (get(f.h, 1) < tol2) {
+                    if (op_run_epi(op, EPI_JACOBI0, o->omega, rhs, xr, rhs, 0, n0, 0, 0, false, false, stv)) return 1;
+                    done = true;
+                    res = xr;
+                } else if (get(f.h, 2) < tol2) {
+                    done = true;
+                    res = bufs[f.buf];
+                }
+            } else if (f.kind == 3) {
+                if (get(f.h, 0) < tol2) {   // stopped after sweep k: x_k, one sweep from the
+                    // launch's input (intact: only one launch was queued after it) into the
+                    // buffer that launch wrote (abandoned)
+                    double* xk = bufs[(f.buf + 1) % nb];
+                    if (op_run_epi(op, EPI_JACOBI, o->omega, bufs[f.in], xk, rhs, 0, n0, 0, 0, false, false, stv))
+                        return 1;
+                    done = true;
+                    res = xk;
+                } else if (get(f.h, 1) < tol2) {
+                    done = true;
+                    res = bufs[f.buf];
+                }
+            } else if (get(f.h) < tol2) {
+                done = true;
+                res = bufs[f.buf];
+            }
+            return failed ? 1 : 0;
+        };
+        for (int k = k0; k <= maxit; ++k) {
+            const bool last = k == maxit;
+            const int nxt = (cur + 1) % nb;
+            int h = -1;
+            if (j2 && k + 1 < maxit) {   // sweeps k, k+1: [||dr_k||^2, ||dr_{k+1}||^2]
+                h = arm(H_J0, 2);
+                if (jrun(EPI_JACOBI2, bufs[cur], bufs[nxt], rhs, true, true, h)) return 1;
+                // every open test is read now: a two-sweep launch's own (below) after the
+                // next launch, because the one after that would overwrite its input
+                while (nq > 0) {
+                    bool done;
+                    double* res = nullptr;
+                    if (settle(done, res)) return 1;
+                    if (done) { *out = res; return 0; }
+                }
+                q[nq++] = Pend{3, h, nxt, cur};
+                cur = nxt;
+                ++k;
+                continue;
+            }
+            if (last) {   // the last sweep's norm cannot change the result: x . rhs instead
+                dot_part_n = -1;
+                if (direct() && dot_idx == SC_SRN && op->dot_base < 0 && op->part_off == 0 && !op->part_dst &&
+                    op->form != FORM_STENCIL) {   // its partials wait for pcg_beta_kernel
+                    if (op_run_epi(op, EPI_JACOBI, o->omega, bufs[cur], bufs[nxt], rhs, 0, n0, 0, 0, false, true, stv))
+                        return 1;
+                    dot_part_n = op->last_partials;
+                    dot_part = op->ctx->scratch + dot_part_n;   // (where poms_op_run_reduce2 reads a dot's partials)
+                } else if (run(EPI_JACOBI, bufs[cur], bufs[nxt], rhs, nullptr, sc + dot_idx) || allsum(sc + dot_idx, 1)) {
+                    return 1;
+                }
+            } else {
+                h = arm(H_JN + ring, 1);
+                if (jrun(EPI_JACOBI, bufs[cur], bufs[nxt], rhs, true, false, h)) return 1;
+                ring ^= 1;
+            }
+            cur = nxt;
+            if (nq == depth || (nq > 0 && (q[0].kind == 3 || q[0].kind == 5))) {   // the test of the sweep `depth`
+                bool done;                                      // back, read after this one is queued
+                double* res = nullptr;
+                if (settle(done, res)) return 1;
+                if (done) { *out = res; return 0; }
+            }
+            if (!last) q[nq++] = Pend{1, h, cur, -1};
+        }
+        while (nq > 0) {   // tests still open after the last sweep (its own has none)
+            bool done;
+            double* res = nullptr;
+            if (settle(done, res)) return 1;
+            if (done) { *out = res; return 0; }
+        }
+        *dot_done = k0 <= maxit ? 1 : 0;
+        *out = bufs[cur];
+        return 0;
+    }
+};
+
+}  // namespace
+
+// Speculative smoother call (see PcgRun::spec_*), in two halves: spec_issue queues every
+// launch of the call (and, last, the copy of the device-held sums to the host); the
+// values it needs later are described by R.sparts / schk / srr / sn / vrr0.
+// spec_finish waits for the stream and evaluates the stop tests: 0 done, 1 error, 2 a
+// stop test fired (the caller repeats the call step by step).
+static int spec_issue(PcgRun& R, const double* b, double* x, int has_x0, double* const* work, int* vrr0_out) {
+    poms_op* op = R.op;
+    const poms_pcg_opts* o = R.o;
+    poms_ctx* ctx = op->ctx;
+    const poms_layout* L = &op->L;
+    void* stream = R.stv;
+    double *r = work[0], *q = work[1];
+    double* z[3] = {work[2], work[3], work[4]};
+    if (has_x0) {   // x0 is kept for the step-by-step repeat
+        const int64_t nbak = (int64_t)(op->L.n[0] + 2 * op->L.pads[0]) * row_geom(&op->L).s0;
+        POMS_HIP_CHECK(hipMemcpyAsync(op->spec_bak, x, nbak * sizeof(double), hipMemcpyDeviceToDevice, R.st));
+    }
+    if (!has_x0) {
+        if (poms_vec_fill(ctx, L, 0.0, x, stream)) return 1;
+    } else if (R.run(EPI_RESID, x, r, b, nullptr, nullptr)) {
+        return 1;
+    }
+    const int vrr0 = R.svals(1);
+    *vrr0_out = vrr0;
+    if (!has_x0 ? vec_copy_dot(ctx, L, b, r, op->spec_dev + vrr0, stream)   // r = b and r.r
+                : poms_vec_dot(ctx, L, r, r, op->spec_dev + vrr0, stream))
+        return 1;
+    double* s = nullptr;
+    if (R.spec_damped_jacobi(r, z[0], z[1], SC_SR, &s)) return 1;
+    double* p = s;   // p keeps this buffer; the later psolves use the other two
+    double* fa = nullptr;
+    double* fb = nullptr;
+    for (double* c : z)
+        if (c != p) (fa ? fb : fa) = c;
+    for (int k = 1; k <= o->maxiter; ++k) {
+        if (R.run(EPI_APPLYDOT, p, q, p, nullptr, R.sc + SC_PQ) || R.allsum(R.sc + SC_PQ, 1)) return 1;
+        hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 0);
+        const int vrr = R.svals(1);
+        R.srr.push_back(vrr);
+        if (o->skip_tail && k == o->maxiter) {   // the rest of this iteration is discarded
+            if (poms_pcg_final_update_dev(ctx, L, R.sc + SC_ALPHA, x, p, r, q, op->spec_dev + vrr, stream)) return 1;
+            break;
+        }
+        if (poms_pcg_r_update_dev(ctx, L, R.sc + SC_ALPHA, r, q, op->spec_dev + vrr, stream)) return 1;
+        double* sn = nullptr;
+        if (R.spec_damped_jacobi(r, fa, fb, SC_SRN, &sn)) return 1;
+        hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 1);
+        if (poms_pcg_xp_update_dev(ctx, L, R.sc + SC_ALPHA2, x, p, sn, stream)) return 1;
+    }
+    if (R.sn > poms_op::kSpecVals) { set_error("pcg speculative: too many values"); return 1; }
+    if (R.comm && R.sn > 0 && poms_allreduce_sum(R.comm, op->spec_dev, R.sn, stream, 1)) return 1;
+    if (R.sn > 0)
+        POMS_HIP_CHECK(hipMemcpyAsync(op->spec_host, op->spec_dev, R.sn * sizeof(double), hipMemcpyDeviceToHost, R.st));
+    POMS_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static int spec_finish(PcgRun& R, int vrr0, poms_pcg_info* info) {
+    const poms_pcg_opts* o = R.o;
+    POMS_HIP_CHECK(hipStreamSynchronize(R.st));
+    std::vector<double> v(R.op->spec_host, R.op->spec_host + R.sn);
+    for (const PcgRun::SPart& s : R.sparts) {
+        const bool wn = s.kind & 1, wd = s.kind & 2;
+        const double* reg = R.op->spec_part + s.off;
+        if (wn) v[s.vi + (wd ? 1 : 0)] = PcgRun::host_reduce(reg, s.n);
+        if (wd) v[s.vi] = PcgRun::host_reduce(reg + (wn ? s.n : 0), s.n);
+    }
+    const double tol2 = o->jtol * o->jtol;
+    for (int i : R.schk)
+        if (v[i] < tol2) return 2;
+    const double nrmr0 = std::sqrt(v[vrr0]);
+    for (int i : R.srr)
+        if (v[i] < o->tol * nrmr0) return 2;
+    const double nrmr = R.srr.empty() ? nrmr0 * nrmr0 : v[R.srr.back()];
+    info->niter = o->maxiter;
+    info->success = 0;
+    info->res_norm = std::sqrt(nrmr);
+    return 0;
+}
+
+// One speculative call, through a captured graph of its launches when POMS_PCG_GRAPH
+// is not 0 and there is no host-transport communicator (its callbacks synchronise).
+// Graphs are cached per operator by the call's buffers, options and launch-timing
+// state (kSpecGraphs entries, least recently used replaced).
+static int pcg_speculative(PcgRun& R, const double* b, double* x, int has_x0, double* const* work,
+                           poms_pcg_info* info) {
+    poms_op* op = R.op;
+    const poms_pcg_opts* o = R.o;
+    // POMS_PCG_GRAPH=0: never.  Not with a communicator: the distributed operator call's
+    // ring-slot and exchange bookkeeping is host-side per call (a captured RCCL
+    // loopback call crashed in the attempt, r04graph logs).  A caller whose buffers
+    // never repeat would capture every call: after 8 more captures than hits the
+    // operator stops using graphs.
+    // POMS_PCG_GRAPH=2 (opt-in, tools/graph_rccl_probe.py): graphs with a communicator
+    // too -- every exchange and all-reduce of the call captured; RCCL's point-to-point
+    // exchange does not survive capture, the peer transport's does (POMS_COMM_PEER=1)
+    const char* ge = getenv("POMS_PCG_GRAPH");
+    int host_comm = 0;
+    if (R.comm && poms_comm_is_host(R.comm, &host_comm)) return 1;
+    const bool comm_ok = !R.comm || (ge && ge[0] == '2' && !host_comm);
+    const bool graph = !(ge && ge[0] == '0') && comm_ok && op->spec_graph_caps <= op->spec_graph_hits + 8;
+    if (!graph) {
+        int vrr0 = 0;
+        if (spec_issue(R, b, x, has_x0, work, &vrr0)) return 1;
+        return spec_finish(R, vrr0, info);
+    }
+    uint64_t key[16] = {};
+    auto bits = [](double d) { uint64_t u; std::memcpy(&u, &d, 8); return u; };
+    key[0] = (uint64_t)(uintptr_t)b;
+    key[1] = (uint64_t)(uintptr_t)x;
+    for (int i = 0; i < 5; ++i) key[2 + i] = (uint64_t)(uintptr_t)work[i];
+    key[7] = (uint64_t)has_x0 | ((uint64_t)(o->skip_tail ? 2 : 0)) | ((uint64_t)(uint32_t)o->maxiter << 8) | ((uint64_t)(uint32_t)o->jmaxiter << 40);
+    key[8] = bits(o->tol);
+    key[9] = bits(o->jtol);
+    key[10] = bits(o->omega);
+    key[11] = (uint64_t)(uint32_t)op->variant | ((uint64_t)(uint32_t)op->chunk << 32);
+    key[12] = (uint64_t)(op->timing ? 1 : 0) | ((uint64_t)(uint32_t)op->t_epi << 8) | ((uint64_t)(uint32_t)op->t_every << 32);
+    key[13] = (uint64_t)(uintptr_t)R.comm | ((uint64_t)(uint32_t)(o->prev + 1) << 48) | ((uint64_t)(uint32_t)(o->next + 1) << 56);
+    {   // whatever else changes the captured launches: the setters' generation, the tile
+        // geometry and ghost corners, the partials layout, and the env knobs read per launch
+        const char* hp = getenv("POMS_HOST_PARTIALS");
+        const char* la = getenv("POMS_PCG_LOOKAHEAD");
+        key[14] = op->gen ^ ((uint64_t)(uint32_t)op->tout << 20) ^ ((uint64_t)(op->ghost_corners ? 1 : 0) << 52) ^
+                  ((uint64_t)(uint32_t)(hp ? atoi(hp) + 1 : 0) << 40);
+        key[15] = (uint64_t)(uint32_t)(op->dot_base + 1) ^ ((uint64_t)(uint32_t)op->part_off << 32) ^
+                  ((uint64_t)(la && la[0] ? la[0] : 0) << 56);
+    }
+    poms_op::SpecGraph* hit = nullptr;
+    for (auto& g : op->spec_graphs)
+        if (g.exec && std::memcmp(g.key, key, sizeof(key)) == 0) hit = &g;
+    if (!hit) {   // capture the call's launches once
+        poms_op::SpecGraph* slot = &op->spec_graphs[0];
+        for (auto& g : op->spec_graphs)
+            if (!g.exec || g.use < slot->use) slot = &g;
+        if (slot->exec) {
+            (void)hipGraphExecDestroy(slot->exec);
+            slot->exec = nullptr;
+        }
+        // captured on a private stream (torch's default stream is the null stream, which
+        // cannot be captured); nothing runs until the graph is launched on the caller's
+        if (!op->cap_stream) POMS_HIP_CHECK(hipStreamCreateWithFlags(&op->cap_stream, hipStreamNonBlocking));
+        const hipStream_t cst = R.st;
+        void* const cstv = R.stv;
+        R.st = op->cap_stream;
+        R.stv = op->cap_stream;
+        POMS_HIP_CHECK(hipStreamBeginCapture(R.st, hipStreamCaptureModeRelaxed));
+        int vrr0 = 0;
+        const int rc = spec_issue(R, b, x, has_x0, work, &vrr0);
+        hipGraph_t gr = nullptr;
+        const hipError_t ce = hipStreamEndCapture(R.st, &gr);
+        R.st = cst;
+        R.stv = cstv;
+        ++op->spec_graph_caps;
+        hipGraphExec_t ex = nullptr;
+        hipError_t ie = hipSuccess;
+        if (!rc && ce == hipSuccess) ie = hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0);
+        if (gr) (void)hipGraphDestroy(gr);
+        if (rc || ce != hipSuccess || ie != hipSuccess) {
+            // Nothing captured ran.  Clear the sticky error and run the call uncaptured on
+            // the caller's stream (advisor, round 4: a capture or instantiate failure used
+            // to fail the whole poms_pcg_jacobi call); graphs are off for this operator
+            // from now on.
+            (void)hipGetLastError();
+            op->spec_graph_caps += 1 << 20;
+            R.sparts.clear();
+            R.schk.clear();
+            R.srr.clear();
+            R.scur = 0;
+            R.sn = 0;
+            int vrr0u = 0;
+            if (spec_issue(R, b, x, has_x0, work, &vrr0u)) return 1;
+            return spec_finish(R, vrr0u, info);
+        }
+        std::memcpy(slot->key, key, sizeof(key));
+        slot->exec = ex;
+        slot->parts = R.sparts;
+        slot->chk = R.schk;
+        slot->rr = R.srr;
+        slot->sn = R.sn;
+        slot->vrr0 = vrr0;
+        hit = slot;
+    } else {
+        ++op->spec_graph_hits;
+    }
+    hit->use = ++op->spec_graph_clock;
+    POMS_HIP_CHECK(hipGraphLaunch(hit->exec, R.st));
+    R.sparts = hit->parts;
+    R.schk = hit->chk;
+    R.srr = hit->rr;
+    R.sn = hit->sn;
+    return spec_finish(R, hit->vrr0, info);
+}
+
+// Speculative mode is opt-in (POMS_PCG_SPEC=1): on the 2D 1024^2 cycle, measured in one
+// process against the step-by-step loop, it costs 3.8 ms per cycle vs 3.1 (graph replay
+// included; profiles/r04/graph): the stream drain it needs at the end of every call
+// exposes the host's issue of the next phase, and the step-by-step loop's lazy reads
+// already keep the queue ahead of the GPU.
+static bool pcg_spec_wanted(const poms_op*, const poms_pcg_opts* o) {
+    const char* e = getenv("POMS_PCG_SPEC");
+    return e && e[0] == '1' && o->maxiter >= 1 && o->jmaxiter >= 3;
+}
+
+static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o, const double* b, double* x,
+                           int has_x0, double* const* work, poms_pcg_info* info, void* stream);
+
+// (a peer exchange that timed out during the call fails it: poms_comm_check)
+int poms_pcg_jacobi(poms_op* op, poms_comm* comm, const poms_pcg_opts* o, const double* b, double* x, int has_x0,
+                    double* const* work, poms_pcg_info* info, void* stream) {
+    if (pcg_jacobi_impl(op, comm, o, b, x, has_x0, work, info, stream)) return 1;
+    return comm ? poms_comm_check(comm) : 0;
+}
+
+static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o, const double* b, double* x,
+                           int has_x0, double* const* work, poms_pcg_info* info, void* stream) {
+    if (!op || !o || !b || !x || !work || !info) { set_error("poms_pcg_jacobi: null argument"); return 1; }
+    for (int i = 0; i < 5; ++i)
+        if (!work[i]) { set_error("poms_pcg_jacobi: null work vector"); return 1; }
+    if (o->maxiter < 0 || o->jmaxiter < 1) { set_error("poms_pcg_jacobi: bad iteration counts"); return 1; }
+    POMS_HIP_CHECK(hipSetDevice(op->ctx->device));
+    if (!op->sv_dev) {
+        POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->sv_dev), SC_N * sizeof(double)));
+        POMS_HIP_CHECK(hipMemset(op->sv_dev, 0, SC_N * sizeof(double)));
+        // coherent (fine-grained) and device-mapped: reduction kernels write the
+        // host-read norms straight into it
+        POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&op->sv_host), poms_op::kSvRing * sizeof(double),
+                                     hipHostMallocMapped | hipHostMallocCoherent));
+        POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&op->sv_part),
+                                     (size_t)poms_op::kSvRing * poms_op::kSvPart * sizeof(double),
+                                     hipHostMallocMapped | hipHostMallocCoherent));
+        PcgRun::part_arm(op->sv_part, poms_op::kSvRing * poms_op::kSvPart);
+        for (int64_t& q : op->sv_seq) q = -1;
+    }
+    if (pcg_spec_wanted(op, o)) {
+        const int64_t nbak = (int64_t)(op->L.n[0] + 2 * op->L.pads[0]) * row_geom(&op->L).s0;
+        if (!op->spec_dev) {
+            POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->spec_dev), poms_op::kSpecVals * sizeof(double)));
+            POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&op->spec_host), poms_op::kSpecVals * sizeof(double),
+                                         hipHostMallocDefault));
+            POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&op->spec_part), poms_op::kSpecPart * sizeof(double),
+                                         hipHostMallocMapped | hipHostMallocCoherent));
+        }
+        if (has_x0 && op->spec_bak_n < nbak) {
+            if (op->spec_bak) POMS_HIP_CHECK(hipFree(op->spec_bak));
+            op->spec_bak = nullptr;
+            op->spec_bak_n = 0;
+            POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->spec_bak), nbak * sizeof(double)));
+            op->spec_bak_n = nbak;
+        }
+        PcgRun RS{op, comm, o, as_stream(stream), stream, op->sv_dev, op->sv_host};
+        RS.n0 = op->ndim == 3 ? op->L.n[0] : 1;
+        ++op->spec_calls;
+        const int rc = pcg_speculative(RS, b, x, has_x0, work, info);
+        if (rc != 2) return rc;
+        ++op->spec_repeats;
+        // a stop test fired: the step-by-step loop from the same inputs
+        if (has_x0)
+            POMS_HIP_CHECK(hipMemcpyAsync(x, op->spec_bak, nbak * sizeof(double), hipMemcpyDeviceToDevice, as_stream(stream)));
+    }
+    PcgRun R{op, comm, o, as_stream(stream), stream, op->sv_dev, op->sv_host};
+    R.n0 = op->ndim == 3 ? op->L.n[0] : 1;
+    poms_ctx* ctx = op->ctx;
+    const poms_layout* L = &op->L;
+    double *r = work[0], *q = work[1];
+    double* z[3] = {work[2], work[3], work[4]};
+    // x0 = None: x = 0, r = b - A.0 = b exactly; else r = b - A x0
+    if (!has_x0) {
+        if (poms_vec_fill(ctx, L, 0.0, x, stream)) return 1;
+    } else if (R.run(EPI_RESID, x, r, b, nullptr, nullptr)) {
+        return 1;
+    }
+    const int hrr0 = R.arm(H_RR0, 1);
+    {
+        double* d = R.hslot(hrr0);
+        if (!d) return 1;
+        if (!has_x0 ? vec_copy_dot(ctx, L, b, r, d, stream)   // r = b and r.r in one pass
+                    : poms_vec_dot(ctx, L, r, r, d, stream))
+            return 1;
+        if (R.lazy_post(hrr0, 1)) return 1;
+    }
+    const double nrmr0 = std::sqrt(R.get(hrr0));
+    if (R.failed) return 1;
+    // Two-sweep lookahead in the damped-Jacobi calls (one rank; POMS_PCG_LOOKAHEAD=1 /
+    // 0 forces it on / off, default on for 2D operators, where the host's turn-around
+    // per sweep is close to a sweep's GPU time): a fourth preconditioner buffer
+    double* e4 = nullptr;
+    {
+        const char* le = getenv("POMS_PCG_LOOKAHEAD");
+        const bool la = R.direct() && (le && le[0] ? le[0] == '1' : op->ndim == 2);
+        if (la) {
+            // The buffer takes the work vectors' 16-B / 128-B phase (they start `shift`
+            // doubles into their allocation on the line-aligned layout): the flat vector
+            // kernels and v5's aligned tiles then run on it exactly as on the other three
+            // buffers, with the same block split of the sums (advisor, round 4).
+            const int64_t nbuf = (int64_t)(op->L.n[0] + 2 * op->L.pads[0]) * row_geom(&op->L).s0;
+            const int64_t off = (int64_t)((reinterpret_cast<uintptr_t>(work[2]) & 127) / sizeof(double));
+            if (op->la_n < nbuf) {
+                if (op->la_raw) POMS_HIP_CHECK(hipFree(op->la_raw));
+                op->la_raw = op->la_buf = nullptr;
+                op->la_n = 0;
+                POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->la_raw), (nbuf + 16) * sizeof(double)));
+                op->la_n = nbuf;
+                op->la_off = -1;
+            }
+            if (op->la_off != off) {   // (re-)placed: zero ghosts
+                POMS_HIP_CHECK(hipMemsetAsync(op->la_raw, 0, (nbuf + 16) * sizeof(double), R.st));
+                op->la_off = off;
+                op->la_buf = op->la_raw + off;
+            }
+            e4 = op->la_buf;
+        }
+    }
+    double* s = nullptr;
+    int dd = 0;
+    if (R.damped_jacobi(r, z[0], z[1], SC_SR, &s, &dd, e4)) return 1;
+    if (!dd && R.dot(s, r, R.sc + SC_SR)) return 1;
+    double* p = s;   // p keeps this buffer; later psolves use the others
+    double* fp[3] = {nullptr, nullptr, nullptr};
+    {
+        int nf = 0;
+        for (double* c : {z[0], z[1], z[2], e4})
+            if (c && c != p) fp[nf++] = c;
+    }
+    double* fa = fp[0];
+    double* fb = fp[1];
+    double* fc = fp[2];   // (nullptr without the lookahead)
+    int k = 0;
+    double nrmr = nrmr0 * nrmr0;
+    for (k = 1; k <= o->maxiter; ++k) {
+        if (R.apd_alpha(p, q)) return 1;
+        const int hrr = R.arm(H_RR, 1);
+        if (o->skip_tail && k == o->maxiter) {
+            // the reference goes on to s = psolve(A, r), s.r, beta and p (`sources/solvers.py:117-124`)
+            // and returns without reading any of them: x and r.r only
+            if (R.rupd(r, q, hrr, x, p)) return 1;
+            nrmr = R.get(hrr);
+            if (R.failed) return 1;
+            if (nrmr < o->tol * nrmr0) {   // x as the early-stop branch below rounds it: the final pass left it in r
+                if (poms_vec_scale(ctx, L, 1.0, r, x, stream)) return 1;
+                k -= 1;
+            }
+            break;
+        }
+        if (R.rupd(r, q, hrr)) return 1;
+        double* sn = nullptr;
+        if (R.damped_jacobi(r, fa, fb, SC_SRN, &sn, &dd, fc)) return 1;   // queued before the read
+        if (!dd && R.dot(sn, r, R.sc + SC_SRN)) return 1;
+        nrmr = R.get(hrr);
+        if (R.failed) return 1;
+        if (nrmr < o->tol * nrmr0) {   // the reference stops before psolve: that one is discarded
+            if (poms_vec_axpby_dev(ctx, L, R.sc + SC_ONE, x, p, x, stream)) return 1;
+            k -= 1;
+            break;
+        }
+        // beta folded into the x/p update where it can be (one rank, small grids)
+        const int fb = (dd && R.dot_part_n >= 0) ? R.xpupd_beta(x, p, sn) : 1;
+        if (fb < 0) return 1;
+        if (fb > 0) {
+            if (R.fix_sr()) return 1;
+            if (dd && R.dot_part_n >= 0)   // x . rhs's partials from the last sweep, reduced here
+                hipLaunchKernelGGL(pcg_beta_kernel, dim3(1), dim3(256), 0, R.st, R.dot_part, (int)R.dot_part_n, R.sc);
+            else
+                hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 1);
+            if (poms_pcg_xp_update_dev(ctx, L, R.sc + SC_ALPHA2, x, p, sn, stream)) return 1;
+        }
+    }
+    // (a folded beta's pending s.r_old <- s.r_new is dropped: the next call's first
+    // psolve writes s.r before anything reads it)
+    R.sr_stale = false;
+    if (R.flush_alpha()) return 1;
+    if (k > o->maxiter) k = o->maxiter;
+    info->niter = k;
+    info->success = nrmr < o->tol * nrmr0 ? 1 : 0;
+    info->res_norm = std::sqrt(nrmr);
+    POMS_HIP_CHECK(hipGetLastError());
+    return 0;
+}

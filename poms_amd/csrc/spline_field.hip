@@ -21,11 +21,12 @@
 #include <vector>
 
 #include "common.hpp"
+#include "launchers.hpp"     // (these two through abi_internal.hpp; named for the
+#include "split_hooks.hpp"   // build's dependency scan, which reads this file only)
+#include "abi_internal.hpp"
 #include "poms_hip.h"
 
 namespace poms {
-
-int ctx_device(const poms_ctx* ctx);   // poms_abi.hip
 
 namespace {
 

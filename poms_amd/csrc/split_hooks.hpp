@@ -1,4 +1,5 @@
-// Shared by poms_abi.hip (op_run_split) and comm.hip (poms_op_run_dist).
+// Shared by abi_op.hip (op_run_split, declared in abi_internal.hpp) and comm.hip
+// (poms_op_run_dist).
 #pragma once
 
 namespace poms {

@@ -13,6 +13,7 @@
 // shared with its neighbours).  One thread per output row, grid-stride, per-block
 // partial sums for the Jacobi norm and the fused dots.
 #include "common.hpp"
+#include "launchers.hpp"
 
 namespace poms {
 

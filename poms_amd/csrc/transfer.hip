@@ -10,7 +10,8 @@
 // columns with zeros).  The dominant pass (axis 0 of the fine slab) streams the
 // fine vector once: 8 B/DOF for restriction, 16 B/DOF for prolong-add.
 // Coarse extents > 32 (multilevel hierarchies) use the banded gather kernels.
-#include "transfer.hpp"
+#include "common.hpp"
+#include "launchers.hpp"
 
 #include <algorithm>
 #include <cstdlib>

@@ -6,14 +6,11 @@
 // unit-stride axis i2 (coalesced 8-B accesses); grid-stride over rows.
 // HBM-bound: 16-32 B per DOF, no reuse.
 #include "common.hpp"
+#include "launchers.hpp"
 
 #include <cstdlib>
 
 namespace poms {
-
-enum VecOp : int { V_AXPBY = 0, V_SCALE = 1, V_FILL = 2, V_DOT = 3, V_PCGUPD = 4, V_RUPD = 5, V_XPUPD = 6,
-                  V_SCALEDOT = 7 /* z = a x and z.z (flat kernel only) */,
-                  V_FINUPD = 8 /* pcg's last iteration, see stop_update */ };
 
 // grid caps (= partial sums per launch): the flat vector kernels run one pass per
 // thread up to 65536 blocks of 256 (grid-stride beyond): at 515^3 the r update

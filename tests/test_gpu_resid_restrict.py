@@ -99,6 +99,41 @@ def test_resid_restrict_ignores_ghosts(gpu):
     assert torch.equal(tr.resid_restrict(A, b, x), rc)
 
 
+@pytest.mark.parametrize("nd,p,Nf,Nc,form", [(2, 3, 64, 8, "sum"), (3, 3, 64, 8, "sum")])
+def test_resid_restrict_first_call_under_capture(gpu, nd, p, Nf, Nc, form):
+    """A transfer's very first resid_restrict may be captured into a graph: set_operator
+    has sized the chunk partials, the call allocates nothing.  n = 67 per axis, the
+    smallest extent whose passes run in 4 chunks (fine extent >= 64 and fewer than 32768
+    lines: 67 in 2D, 67^2 in 3D), so the partial-sum buffer is really used.  Replays
+    equal the eager result of an independent set-up bitwise, also after x changed."""
+    rng = np.random.default_rng(23)
+    V, A, tr, _, n = _setup(nd, p, Nf, Nc, form)
+    xg, bg = rng.uniform(-1, 1, (n,) * nd), rng.uniform(-1, 1, (n,) * nd)
+    xg2 = rng.uniform(-1, 1, (n,) * nd)
+    x, b = V.zeros().from_numpy(xg), V.zeros().from_numpy(bg)
+    want = tr.resid_restrict(A, b, x).clone()
+    want2 = tr.resid_restrict(A, b, V.zeros().from_numpy(xg2)).clone()
+    assert not torch.equal(want, want2)
+
+    Vc, Ac, trc, _, _ = _setup(nd, p, Nf, Nc, form)
+    assert trc.set_operator(Ac)
+    xc, bc = Vc.zeros().from_numpy(xg), Vc.zeros().from_numpy(bg)
+    x2 = Vc.zeros().from_numpy(xg2)
+    out = torch.full_like(trc.coarse_empty(), float("nan"))
+    st = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=st):
+        trc.resid_restrict(Ac, bc, xc, out=out)
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(out, want)
+    xc._data.copy_(x2._data)
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(out, want2)
+
+
 def test_resid_restrict_refuses_banded(gpu):
     """Coarse extents > 32 (banded transfers): set_operator says no, and the multilevel
     V-cycle keeps residual + restriction on those levels."""
