@@ -603,6 +603,71 @@ int poms_field_load(poms_field* field, const double* f, int64_t q0b, int64_t q0e
 int poms_field_error(poms_field* field, const double* x, const int* der, const double* u, int64_t q0b,
                      int64_t q0e, double* acc, void* stream);
 
+/* ---- spline fields at scattered points ------------------------------------------ */
+/* Gather (u_h and its gradient at N positions) and scatter (the load vector of point
+ * sources, b[i] = sum_k w_k B_i(x_k): charge deposition) for positions held in a DEVICE
+ * array that may change every step.  The span search and the Cox-de Boor triangle run in
+ * the kernels; they stand in for the host-only `splines.find_span` / `basis_funs_ders`
+ * of this package, and the scatter for the placeholder right-hand side
+ * (`sources/mg_jac.py:57-62`) when the sources are points.
+ * Per axis d (HOST arrays, all three axes; an unused leading axis has p = 0 and the two
+ * knots {0, 1}): p[d] the degree (1..5), knots[d] the nknots[d] knots, non-decreasing
+ * and open, with nknots - p - 1 == layout->n[d] and p == layout->pads[d].  The handle
+ * uploads the knots, the nel + 1 breakpoints of the non-empty spans and the span of each
+ * of the nel elements.  Where the breakpoints are uniform the element is guessed from
+ * (x - a) / h and then corrected against the stored breakpoints, elsewhere found by
+ * binary search on them: every point lands in the span `find_span` gives, also on a
+ * breakpoint or 1 ulp beside one.
+ * Positions: one contiguous DEVICE array (ndim, N) in C order, axis d at pos + d N (the
+ * used axes only).  N = 0 launches nothing.  A point is outside if x < T[p] or x > T[n]
+ * on any axis or a coordinate is NaN (x == T[n] is inside, in the last non-empty span):
+ * its cell is -1, its value 0, and it deposits nothing.  Element indices are clamped into
+ * [0, nel - 1] before use, so no verdict can address outside the vector.
+ * The handle owns its tables and the scratch of the binned deposit (at most scratch_bytes:
+ * Pi(p_d + 1) doubles per cell of a slab of elements of the first used axis); the run
+ * calls allocate,
+ * free and synchronise nothing and may be the first calls inside a graph capture.
+ * Distributed (slab) spaces are not supported: layout->n[0] is the global extent.      */
+typedef struct poms_points poms_points;
+int poms_points_create(poms_ctx* ctx, int ndim, const poms_layout* layout, const int* p, const int64_t* nknots,
+                       const double* const* knots, int64_t scratch_bytes, poms_points** points);
+int poms_points_destroy(poms_points* points);
+/* info[0] cells (the product of nel over the axes), info[1] the most elements of the first
+ * used axis one poms_points_deposit_binned call may cover, info[2..4] nel and info[5..7] 1 where the
+ * breakpoints are uniform, per stored axis.                                              */
+int poms_points_info(poms_points* points, int64_t* info);
+/* cell[k]: linear C-order index of point k over the non-empty spans of the used axes,
+ * -1 outside.  Replaces a host loop over `splines.find_span`.                           */
+int poms_points_cells(poms_points* points, const double* pos, int64_t N, int64_t* cell, void* stream);
+/* what = 0: out[N] = u_h(x_k); what = 1 + d: the first derivative along used axis d;
+ * what = -1: out[(1 + ndim), N] = value, then the gradient, from one load of the
+ * Pi(p_d + 1) coefficients of each point.  x: DEVICE padded vector of `layout`.  One
+ * thread per point, the 1D rows from the triangle of `splines.basis_funs_ders` in
+ * registers.  Every output is the same chain of instructions whichever `what` asks for
+ * it: what = -1 equals the separate calls bitwise.                                      */
+int poms_points_eval(poms_points* points, const double* x, const double* pos, int64_t N, int what, double* out,
+                     void* stream);
+/* b[i] += sum_k w_k B_i(x_k) by one FP64 atomic add per point and local basis function
+ * (w NULL: unit weights): a right-hand side of point sources where the reference has the
+ * placeholder b = 1 (`sources/mg_jac.py:57-62`); B_i(x_k) as `splines.basis_funs_ders`.  The simple form: its bits depend on the order in which the
+ * adds arrive, so two calls may differ in the last bits.  b: DEVICE padded vector; ghost
+ * cells and dead pitch columns are not written.                                          */
+int poms_points_deposit_atomic(poms_points* points, const double* pos, const double* w, int64_t N, double* b,
+                               void* stream);
+/* b[i] (+)= the same sum over the points of the cells whose element along the first used
+ * axis lies in [e0b, e0e), with no atomics.  perm (N): DEVICE permutation ordering the points by cell, points outside
+ * last; cell_start (cells + 1): DEVICE offsets of every cell in that order (not only the
+ * slab's).  Stage 1, one wave per cell, adds w_k B_a(x_k) per local basis function a in
+ * perm order and stores the cell's Pi(p_d + 1) sums; stage 2, one thread per DOF, adds the
+ * blocks of the cells in its support in lexicographic cell order.  The bits depend on the
+ * slabs [e0b, e0e) the caller walks and on the order of the points inside each cell, and
+ * on nothing else.  accumulate = 0 overwrites the interior (0 where no point of the slab
+ * reaches): the first slab of a walk; ghost cells and dead pitch columns are not written.
+ * An entry of perm outside [0, N) deposits nothing.                                      */
+int poms_points_deposit_binned(poms_points* points, const double* pos, const double* w, int64_t N,
+                               const int64_t* perm, const int64_t* cell_start, int64_t e0b, int64_t e0e,
+                               int accumulate, double* b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

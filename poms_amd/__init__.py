@@ -21,6 +21,7 @@ __all__ = [
     "pcg_glt", "pcg_kron", "KronSolver", "kron_solve_serial", "kron_solve_par", "to_bnd",
     "collocation_cardinal_splines", "MultilevelVCycle", "crl", "assemble_stencil",
     "QuadGrid", "PointGrid", "assemble_rhs", "evaluate", "l2_error",
+    "SplinePoints", "Binning", "evaluate_at", "deposit",
 ]
 
 
@@ -35,6 +36,12 @@ def __getattr__(name):
     if name in ("QuadGrid", "PointGrid", "assemble_rhs", "evaluate", "l2_error"):
         from . import field
         return getattr(field, name)
+    if name in ("evaluate_at", "deposit"):
+        from . import field
+        return getattr(field, name)
+    if name in ("SplinePoints", "Binning"):
+        from . import points
+        return getattr(points, name)
     if name in ("KronSolver", "kron_solve_serial", "kron_solve_par", "to_bnd"):
         from . import kron_solve
         return getattr(kron_solve, name)

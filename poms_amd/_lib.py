@@ -162,6 +162,13 @@ _SIGS = {
     "poms_field_eval": [_vp, _vp, C.POINTER(_i), _i64, _i64, _vp, _vp],
     "poms_field_load": [_vp, _vp, _i64, _i64, _i, _vp, _vp],
     "poms_field_error": [_vp, _vp, C.POINTER(_i), _vp, _i64, _i64, _vp, _vp],
+    "poms_points_create": [_vp, _i, _LP, C.POINTER(_i), C.POINTER(_i64), _vp, _i64, _pp],
+    "poms_points_destroy": [_vp],
+    "poms_points_info": [_vp, C.POINTER(_i64)],
+    "poms_points_cells": [_vp, _vp, _i64, _vp, _vp],
+    "poms_points_eval": [_vp, _vp, _vp, _i64, _i, _vp, _vp],
+    "poms_points_deposit_atomic": [_vp, _vp, _vp, _i64, _vp, _vp],
+    "poms_points_deposit_binned": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i, _vp, _vp],
 }
 _RESTYPES = {"poms_last_error": C.c_char_p}
 

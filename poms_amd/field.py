@@ -259,3 +259,17 @@ def evaluate(V, knots, x, points, der=None) -> torch.Tensor:
 def l2_error(V, knots, x, u, nquad: int | None = None) -> float:
     """``‖u_h − u‖`` in L2 (see :meth:`QuadGrid.l2_error`)."""
     return QuadGrid(V, knots, nquad).l2_error(x, u)
+
+
+def evaluate_at(V, knots, x, pos, der=None) -> torch.Tensor:
+    """``u_h`` of ``x`` at the scattered points ``pos``, a ``(ndim, N)`` device tensor
+    (see :meth:`poms_amd.points.SplinePoints.evaluate`)."""
+    from .points import SplinePoints
+    return SplinePoints(V, knots).evaluate(x, pos, der)
+
+
+def deposit(V, knots, pos, w=None) -> StencilVector:
+    """Load vector ``b[i] = Σ_k w_k B_i(x_k)`` of point sources at ``pos``
+    (see :meth:`poms_amd.points.SplinePoints.deposit`)."""
+    from .points import SplinePoints
+    return SplinePoints(V, knots).deposit(pos, w)
