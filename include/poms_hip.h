@@ -122,6 +122,26 @@ int poms_op_assemble_stencil(poms_ctx* ctx, int ndim, const poms_layout* layout,
 /* The coefficients of a general-stencil operator in the spl StencilMatrix._data
  * layout (the layout poms_op_create_stencil takes), HOST output.               */
 int poms_op_stencil_data(poms_op* op, double* data_host);
+/* Galerkin coarse operator Ac = P^T A P of a general-stencil operator A = `fine`,
+ * P = P0 (x) P1 (x) P2, on the device.  Replaces `Ac = R.dot(Af).dot(P)`
+ * (`sources/mg_jac.py:80-81`), there a scipy product of the assembled matrix.  Ac is
+ * again a stencil of A's half-widths p_d on the coarse space and is formed one axis
+ * at a time (axis 0, then 1, then 2),
+ *   S'[.., I, .., kc, ..] = sum_{i,k} P_d[i,I] P_d[i+k-p_d, I+kc-p_d] S[.., i, .., k, ..],
+ * by gather passes without atomics: two calls give the same bits.  nf, nc, P follow
+ * poms_transfer_create: P[d] HOST dense row-major nf[d] x nc[d], unused leading axes
+ * 1 x 1 ones.  The result is a general-stencil operator on `coarse_layout` (every
+ * entry point that takes poms_op_create_stencil's takes it); couplings to columns
+ * outside the coarse grid are exact zeros.  Checked before any launch (status 1 and
+ * a message): `fine` is an undistributed general stencil (g0 = 0, whole axis 0, no
+ * POMS_LAYOUT_GHOST_DATA); nf equals its rows; coarse_layout->n = nc and its pads
+ * equal the fine half-widths; no column of P is empty; the product fits the pads,
+ * i.e. the row supports of two columns more than p_d apart are more than p_d apart.
+ * A set-up call: it allocates and frees its scratch (the two intermediates, about
+ * 1/2 and 1/4 of the fine coefficients), runs on the null stream, ends in a device
+ * synchronise and cannot be captured into a graph.                              */
+int poms_op_galerkin_stencil(poms_op* fine, const poms_layout* coarse_layout, const int64_t* nf,
+                             const int64_t* nc, const double* const* P, poms_op** coarse);
 int poms_op_destroy(poms_op* op);
 /* Planes per workgroup along axis 0 (3D); 0 = automatic. */
 int poms_op_set_chunk(poms_op* op, int chunk);

@@ -22,6 +22,7 @@ __all__ = [
     "collocation_cardinal_splines", "MultilevelVCycle", "crl", "assemble_stencil",
     "QuadGrid", "PointGrid", "assemble_rhs", "evaluate", "l2_error",
     "SplinePoints", "Binning", "evaluate_at", "deposit",
+    "galerkin_stencil", "GalerkinVCycle",
 ]
 
 
@@ -51,10 +52,10 @@ def __getattr__(name):
     if name in ("kron_dot_v2", "kron_dot_pyccel_2d"):
         from . import kron_product
         return getattr(kron_product, name)
-    if name in ("knots_to_insert", "KronTransfer"):
+    if name in ("knots_to_insert", "KronTransfer", "galerkin_stencil"):
         from . import multilevels
         return getattr(multilevels, name)
-    if name in ("TwoLevelVCycle", "MultilevelVCycle"):
+    if name in ("TwoLevelVCycle", "MultilevelVCycle", "GalerkinVCycle"):
         from . import mg
         return getattr(mg, name)
     if name == "SlabDistribution":

@@ -70,6 +70,7 @@ _SIGS = {
     "poms_op_assemble_stencil": [_vp, _i, _LP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _i64,
                                  _pp],
     "poms_op_stencil_data": [_vp, _vp],
+    "poms_op_galerkin_stencil": [_vp, _LP, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_void_p), _pp],
     "poms_op_set_chunk": [_vp, _i],
     "poms_op_set_tile_cols": [_vp, _i],
     "poms_op_set_variant": [_vp, _i],

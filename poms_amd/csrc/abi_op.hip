@@ -363,6 +363,149 @@ int poms_op_stencil_data(poms_op* o, double* data_host) {
     return 0;
 }
 
+// Galerkin coarse operator P^T A P of a general stencil (csrc/stencil_galerkin.hip).
+// The passes index with the tables built here unguarded: every check comes first.
+int poms_op_galerkin_stencil(poms_op* fine, const poms_layout* coarse_layout, const int64_t* nf, const int64_t* nc,
+                             const double* const* P, poms_op** coarse) {
+    const std::string fn = "poms_op_galerkin_stencil: ";
+    if (!fine || !coarse_layout || !nf || !nc || !P || !coarse) { set_error(fn + "null argument"); return 1; }
+    if (fine->form != FORM_STENCIL || !fine->coef) { set_error(fn + "needs a general-stencil operator"); return 1; }
+    if (!layout_ok(coarse_layout)) { set_error(fn + "bad coarse layout"); return 1; }
+    if (fine->g0 != 0 || (fine->ndim == 3 && fine->L.n[0] != fine->n0g) ||
+        ((fine->L.flags | coarse_layout->flags) & POMS_LAYOUT_GHOST_DATA)) {
+        set_error(fn + "distributed operators (slabs, Cart blocks) are not supported");
+        return 1;
+    }
+    const int d0 = 3 - fine->ndim;
+    int64_t wtot = 1;
+    for (int d = 0; d < 3; ++d) {
+        const std::string ax = "axis " + std::to_string(d) + ": ";
+        if (!P[d]) { set_error(fn + ax + "null prolongation factor"); return 1; }
+        if (nf[d] != fine->L.n[d]) { set_error(fn + ax + "nf does not match the fine operator's rows"); return 1; }
+        if (nc[d] < 1 || nc[d] != coarse_layout->n[d]) { set_error(fn + ax + "nc does not match the coarse layout"); return 1; }
+        if (coarse_layout->pads[d] != fine->sp[d]) {
+            set_error(fn + ax + "the coarse pads must equal the fine stencil half-widths");
+            return 1;
+        }
+        if (d < d0 && (nf[d] != 1 || nc[d] != 1)) { set_error(fn + ax + "unused leading axes need nf = nc = 1"); return 1; }
+        if (fine->sp[d] < 0 || fine->sp[d] > 5) { set_error(fn + ax + "stencil half-width above 5"); return 1; }
+        wtot *= 2 * fine->sp[d] + 1;
+    }
+    if (wtot * nf[0] * nf[1] * nf[2] * 8 > ((int64_t)1 << 40) || nf[0] * nf[1] * nf[2] > 0x7fffffffLL) {
+        set_error(fn + "coefficients too large");
+        return 1;
+    }
+    // per used axis: the row support [lo, lo + cnt) of every column, then the products
+    // wt[I][ii][k][kc] = P[lo[I] + ii, I] P[lo[I] + ii + k - p, I + kc - p]
+    std::vector<int> lo[3], cnt[3];
+    std::vector<double> wt[3];
+    int smax[3] = {1, 1, 1};
+    for (int d = d0; d < 3; ++d) {
+        const std::string ax = "axis " + std::to_string(d) + ": ";
+        const int64_t m = nf[d], n = nc[d];
+        const int p = fine->sp[d], w = 2 * p + 1;
+        const double* Pd = P[d];
+        lo[d].assign(n, 0);
+        cnt[d].assign(n, 0);
+        for (int64_t I = 0; I < n; ++I) {
+            int64_t a = m, b = -1;
+            for (int64_t i = 0; i < m; ++i)
+                if (Pd[i * n + I] != 0.0) { a = std::min(a, i); b = i; }
+            if (b < 0) { set_error(fn + ax + "column " + std::to_string(I) + " of P is empty"); return 1; }
+            lo[d][I] = (int)a;
+            cnt[d][I] = (int)(b - a + 1);
+            smax[d] = std::max(smax[d], cnt[d][I]);
+        }
+        // columns more than p apart must not meet through a fine coupling (|i - j| <= p)
+        for (int64_t I = 0; I < n; ++I)
+            for (int64_t J = I + p + 1; J < n; ++J) {
+                const int hiI = lo[d][I] + cnt[d][I] - 1, hiJ = lo[d][J] + cnt[d][J] - 1;
+                if (std::max(lo[d][J] - hiI, lo[d][I] - hiJ) <= p) {
+                    set_error(fn + ax + "coarse stencil would be wider than the layout's pads");
+                    return 1;
+                }
+            }
+        if ((int64_t)n * smax[d] * w * w > ((int64_t)1 << 27)) { set_error(fn + ax + "weight table too large"); return 1; }
+        wt[d].assign((size_t)(n * smax[d] * w * w), 0.0);
+        for (int64_t I = 0; I < n; ++I)
+            for (int ii = 0; ii < cnt[d][I]; ++ii) {
+                const int64_t i = lo[d][I] + ii;
+                for (int k = 0; k < w; ++k) {
+                    const int64_t j = i + k - p;
+                    if (j < 0 || j >= m) continue;
+                    for (int kc = 0; kc < w; ++kc) {
+                        const int64_t J = I + kc - p;
+                        if (J < 0 || J >= n) continue;
+                        const int64_t e = ((int64_t)ii * w + k) * w + kc;
+                        // (columns contiguous for the axis-2 pass, see GalerkinPass)
+                        wt[d][(size_t)(d < 2 ? I * smax[d] * w * w + e : e * n + I)] = Pd[i * n + I] * Pd[j * n + J];
+                    }
+                }
+            }
+    }
+    POMS_HIP_CHECK(hipSetDevice(fine->ctx->device));
+    auto* o = new poms_op();
+    o->ctx = fine->ctx;
+    o->ndim = fine->ndim;
+    o->form = FORM_STENCIL;
+    o->pmax = fine->pmax;
+    o->L = *coarse_layout;
+    o->g0 = 0;
+    o->n0g = fine->ndim == 3 ? nc[0] : 1;
+    for (int d = 0; d < 3; ++d) o->sp[d] = fine->sp[d];
+    std::vector<void*> tmp;
+    auto dev = [&](const void* h, size_t bytes) -> void* {   // (h null: uninitialised)
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
+        tmp.push_back(p);
+        if (h && hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        return p;
+    };
+    GalerkinPass ps[3];
+    double* bufs[3] = {nullptr, nullptr, nullptr};   // output of each pass
+    int np = 0, rc = 0;
+    int64_t ext[3] = {nf[0], nf[1], nf[2]};
+    for (int d = d0; d < 3 && !rc; ++d, ++np) {
+        GalerkinPass& g = ps[np];
+        g.d = d;
+        for (int e = 0; e < 3; ++e) { g.w[e] = 2 * fine->sp[e] + 1; g.nin[e] = (int)ext[e]; }
+        g.cst_in = ext[0] * ext[1] * ext[2];
+        ext[d] = nc[d];
+        for (int e = 0; e < 3; ++e) g.nout[e] = (int)ext[e];
+        g.cst_out = ext[0] * ext[1] * ext[2];
+        g.smax = smax[d];
+        g.ws_col = d < 2 ? (int64_t)smax[d] * g.w[d] * g.w[d] : 1;
+        g.ws_ent = d < 2 ? 1 : nc[d];
+        g.lo = static_cast<const int*>(dev(lo[d].data(), lo[d].size() * sizeof(int)));
+        g.cnt = static_cast<const int*>(dev(cnt[d].data(), cnt[d].size() * sizeof(int)));
+        g.wt = static_cast<const double*>(dev(wt[d].data(), wt[d].size() * sizeof(double)));
+        if (!g.lo || !g.cnt || !g.wt) rc = 1;
+        if (!rc && d < 2) {   // an intermediate; the last pass writes the operator's planes
+            bufs[np] = static_cast<double*>(dev(nullptr, (size_t)(wtot * g.cst_out) * sizeof(double)));
+            if (!bufs[np]) rc = 1;
+        }
+    }
+    if (!rc && hipMalloc(reinterpret_cast<void**>(&o->coef), (size_t)(wtot * nc[0] * nc[1] * nc[2]) * sizeof(double)) != hipSuccess)
+        rc = 1;
+    if (!rc) {
+        const double* in = fine->coef;
+        for (int s = 0; s < np && !rc; ++s) {
+            double* out = s == np - 1 ? o->coef : bufs[s];
+            rc = galerkin_pass_launch(ps[s], in, out, nullptr);
+            in = out;
+        }
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = 1;
+    }
+    for (void* p : tmp) (void)hipFree(p);
+    if (rc) {
+        set_error(fn + "allocation, upload or launch failed");
+        poms_op_destroy(o);
+        return 1;
+    }
+    *coarse = o;
+    return 0;
+}
+
 int poms_op_destroy(poms_op* o) {
     if (!o) return 0;
     for (double* p : {o->a0t, o->b0t, o->a1, o->b1, o->a2, o->b2, o->dg2a, o->dg2b, o->rdiag0, o->coef, o->sv_dev,

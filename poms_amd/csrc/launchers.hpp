@@ -60,6 +60,27 @@ int stencil_launch(int epi, const StencilGeom& g, const double* coef, const doub
                    const double* b, double omega, double* partial, double* partial2, int max_blocks,
                    hipStream_t st, int* nblk_out);
 
+// ---- stencil_galerkin.hip ---------------------------------------------------------
+// One axis of the Galerkin product P^T A P of a general stencil: coefficient planes
+// [k0][k1][k2] of rows nin -> nout (they differ on axis d only).  Column I of P_d has
+// its non-zero rows in [lo[I], lo[I] + cnt[I]); wt (device, smax * w[d]^2 doubles per
+// column) holds the products P_d[i, I] P_d[i + k - p, I + kc - p]: a column's entries
+// contiguous for the axis-0 and axis-1 passes (ws_ent = 1), the columns contiguous for
+// the axis-2 pass, whose lanes differ in I (ws_col = 1).
+struct GalerkinPass {
+    int d;
+    int w[3];
+    int nin[3], nout[3];
+    int smax;
+    int64_t cst_in, cst_out;   // rows per plane
+    int64_t ws_col, ws_ent;    // weight of (column I, entry e = (ii w + k) w + kc) at wt[I ws_col + e ws_ent]
+    const int* lo;
+    const int* cnt;
+    const double* wt;
+};
+
+int galerkin_pass_launch(const GalerkinPass& g, const double* in, double* out, hipStream_t st);
+
 // ---- transfer.hip -----------------------------------------------------------------
 int transfer_pass_launch(bool restrict_dir, int ncm, const AxisPass& ps, const double* Pm,
                          const double* in, double* out, hipStream_t st, double* part);

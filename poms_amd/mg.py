@@ -287,3 +287,116 @@ class MultilevelVCycle:
         self.infos = [None] * (self.nlevels - 1)
         x = self._level(0, b, x0)
         return x, list(self.infos)
+
+
+class GalerkinVCycle:
+    """V-cycle for a general (variable-coefficient) stencil operator with Galerkin
+    coarse operators, as the reference builds its own (`sources/mg_jac.py:80-81`,
+    ``Ac = R Af P`` of the assembled matrix): ``ops[l+1] = P_l^T ops[l] P_l`` formed on
+    the device (:func:`~poms_amd.multilevels.galerkin_stencil`), every level smoothed
+    by ``pcg(A_l, damped_jacobi, b_l, tol, maxiters[l])`` before and after the coarse
+    correction (:meth:`MultilevelVCycle._level`'s sequence; residual and restriction are
+    two launches, there is no fused pass for stencils) and a dense solve on the
+    coarsest level.
+
+    ``A``: the finest :class:`~poms_amd.stencil.StencilMatrix`; ``P[l]``: the list of
+    1D prolongations, one per axis, from level ``l+1`` to level ``l``.
+    """
+
+    def __init__(self, A, P, *, tol: float = 1e-6, maxiters=None):
+        from .multilevels import galerkin_stencil
+        if len(P) < 1:
+            raise ValueError("the hierarchy needs at least two levels")
+        self.tol = tol
+        self.nlevels = L = len(P) + 1
+        self.maxiters = [10] * (L - 1) if maxiters is None else [int(m) for m in maxiters]
+        if len(self.maxiters) != L - 1:
+            raise ValueError(f"maxiters needs {L - 1} entries")
+        self.P = [[np.ascontiguousarray(p, dtype=np.float64) for p in Pl] for Pl in P]
+        self.ops, self.spaces, self.transfers = [A], [A.space], []
+        for l in range(L - 1):
+            Ac = galerkin_stencil(self.ops[l], self.P[l])
+            self.transfers.append(KronTransfer(self.spaces[l], self.P[l]))
+            self.ops.append(Ac)
+            self.spaces.append(Ac.space)
+        # coarsest level: dense inverse of its Galerkin operator, applied on the device
+        Ac = self.ops[-1].toarray()
+        self.Ac = Ac
+        Ainv = sla.lu_solve(sla.lu_factor(Ac), np.eye(Ac.shape[0]))
+        dev = f"cuda:{self.spaces[0].device}"
+        self.Ainv = torch.from_numpy(np.ascontiguousarray(Ainv)).to(dev)
+        self.rcs = [torch.empty(tr.ncoarse, dtype=F64, device=dev) for tr in self.transfers]
+        self.xc = torch.empty(Ac.shape[0], dtype=F64, device=dev)
+        self.infos = [None] * (L - 1)
+
+    @classmethod
+    def uniform(cls, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *, a=None, c=None,
+                mass_coef: float = 1.0, device=None, tol: float = 1e-6, maxiters=None):
+        """Dyadic uniform hierarchy (as :class:`MultilevelVCycle`'s) under
+        ``-∇·(a∇u) + c u`` assembled on the finest knots by
+        :func:`~poms_amd.assembly.assemble_stencil`."""
+        from .assembly import assemble_stencil
+        if ncells_fine < ncells_coarsest or ncells_coarsest < 1:
+            raise ValueError("need ncells_fine >= ncells_coarsest >= 1")
+        cells = [int(ncells_fine)]
+        while cells[-1] // 2 >= ncells_coarsest and cells[-1] % 2 == 0:
+            cells.append(cells[-1] // 2)
+        if len(cells) < 2:
+            raise ValueError("the hierarchy needs at least two levels (even cell counts)")
+        knots = [uniform_knots(p, N) for N in cells]
+        P1 = [two_level_setup_1d(p, knots[l], knots[l + 1])[2] for l in range(len(cells) - 1)]
+        V = StencilVectorSpace([len(knots[0]) - p - 1] * ndim, [p] * ndim, device=device, align=True)
+        A = assemble_stencil(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef)
+        mg = cls(A, [[P1l] * ndim for P1l in P1], tol=tol, maxiters=maxiters)
+        mg.p, mg.ndim, mg.cells, mg.knots, mg.P1 = int(p), int(ndim), cells, knots, P1
+        return mg
+
+    @property
+    def ndof(self) -> int:
+        return self.spaces[0].dimension
+
+    @property
+    def space(self) -> StencilVectorSpace:
+        return self.spaces[0]
+
+    @property
+    def A(self):
+        return self.ops[0]
+
+    def rhs_ones(self) -> StencilVector:
+        b = self.spaces[0].empty()
+        _lib.call("poms_vec_fill", self.spaces[0].ctx, C.byref(self.spaces[0].layout), 1.0, rt.ptr(b._data),
+                  rt.stream_handle())
+        b._mark_written()
+        b.update_ghost_regions()
+        return b
+
+    def _level(self, l: int, b: StencilVector, x0: StencilVector | None) -> StencilVector:
+        A, tr = self.ops[l], self.transfers[l]
+        x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True)
+        rc = tr.restrict(A.residual(b, x), out=self.rcs[l])
+        if l + 1 == self.nlevels - 1:
+            ec = self.xc
+            _lib.call("poms_dense_matvec", self.spaces[0].ctx, rc.numel(), rt.ptr(self.Ainv), rt.ptr(rc),
+                      rt.ptr(ec), rt.stream_handle())
+        else:
+            Vc = self.spaces[l + 1]
+            bc = Vc.empty()
+            Vc.interior(bc._data).copy_(rc.view(Vc.local_npts))
+            bc._mark_written()
+            bc.update_ghost_regions()
+            ecv = self._level(l + 1, bc, None)
+            ec = Vc.interior(ecv._data).contiguous().view(-1)
+        tr.prolong_add(ec, x)
+        x.update_ghost_regions()
+        x, ipos = pcg(A, damped_jacobi, b, x0=x, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True)
+        if self.infos[l] is None:
+            self.infos[l] = (ipre, ipos)
+        return x
+
+    def cycle(self, b: StencilVector, x0: StencilVector | None = None):
+        """One V-cycle from level 0; returns ``(x, infos)``, ``infos[l] = (info_pre,
+        info_post)`` of level l's first visit in this cycle."""
+        self.infos = [None] * (self.nlevels - 1)
+        x = self._level(0, b, x0)
+        return x, list(self.infos)

@@ -7,6 +7,8 @@
   by sum-factorised device passes (``poms_restrict`` / ``poms_prolong_add``),
   replacing the materialised ``scipy.sparse.kron`` products of
   `sources/mg_jac.py:67-70,94,102`.
+* :func:`galerkin_stencil` -- the coarse operator ``P^T A P`` of a general stencil,
+  on the device (`sources/mg_jac.py:80-81`).
 """
 from __future__ import annotations
 
@@ -34,6 +36,49 @@ def knots_to_insert(Tf, nf, pf, Tc, nc, pc):
     cand = Tf[pf + 1:nf]
     present = np.isin(cand, Tc[pc + 1:nc + 1])
     return np.ascontiguousarray(cand[~present])
+
+
+def galerkin_stencil(A, P: Sequence[np.ndarray], coarse_space: StencilVectorSpace | None = None):
+    """Galerkin coarse operator ``Ac = P^T A P`` of the general stencil ``A`` with
+    ``P = P0⊗P1⊗P2`` (`sources/mg_jac.py:80-81`, there ``R.dot(Af).dot(P)`` of the
+    assembled scipy matrices), formed on the device one axis at a time
+    (``poms_op_galerkin_stencil``).  ``P[d]`` is the dense 1D prolongation of axis
+    ``d`` (fine rows x coarse columns).  The result is a
+    :class:`~poms_amd.stencil.StencilMatrix` of ``A``'s half-widths on
+    ``coarse_space`` (default: a new space of the coarse extents with ``A.space``'s
+    pads, device and alignment)."""
+    from .stencil import StencilMatrix
+    if not isinstance(A, StencilMatrix):
+        raise TypeError("galerkin_stencil needs a StencilMatrix (Kronecker operators have per-axis host products)")
+    V = A.space
+    if V.is_distributed or V.is_cart:
+        raise NotImplementedError("galerkin_stencil: distributed (slab / Cart) spaces are not supported")
+    nd = V.ndim
+    if len(P) != nd:
+        raise ValueError("need one 1D prolongation factor per axis")
+    Ps = [np.ascontiguousarray(p, dtype=np.float64) for p in P]
+    if any(p.ndim != 2 or p.size == 0 for p in Ps):
+        raise ValueError("every prolongation factor must be a non-empty 2D array")
+    ncs = tuple(p.shape[1] for p in Ps)
+    if coarse_space is None:
+        coarse_space = StencilVectorSpace(ncs, V.pads, device=V.device, align=V.aligned)
+    Vc = coarse_space
+    if Vc.is_distributed or Vc.is_cart:
+        raise NotImplementedError("galerkin_stencil: distributed (slab / Cart) spaces are not supported")
+    if Vc.ndim != nd or Vc.device != V.device:
+        raise ValueError("the coarse space must have the fine space's dimension and device")
+    lead = 3 - nd
+    ones = np.ones((1, 1))
+    P3 = [ones] * lead + Ps
+    nf_arr = (C.c_int64 * 3)(*[p.shape[0] for p in P3])
+    nc_arr = (C.c_int64 * 3)(*[p.shape[1] for p in P3])
+    parr = (C.c_void_p * 3)(*[p.ctypes.data_as(C.c_void_p) for p in P3])
+    h = C.c_void_p()
+    try:
+        _lib.call("poms_op_galerkin_stencil", A._h, C.byref(Vc.layout), nf_arr, nc_arr, parr, C.byref(h))
+    except _lib.PomsError as e:
+        raise ValueError(str(e)) from None
+    return StencilMatrix._from_handle(Vc, h)
 
 
 class KronTransfer:
