@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define POMS_ABI_VERSION 4 /* 4: poms_pcg_opts.skip_tail, poms_pcg_final_update_dev */
+#define POMS_ABI_VERSION 5 /* 5: poms_op_create_matfree, poms_op_diagonal */
 
 /* operator forms (see poms_op_create) */
 #define POMS_FORM_SINGLE 0 /* y = F0 (x) F1 (x) F2 x                                  */
@@ -119,6 +119,36 @@ int poms_op_assemble_stencil(poms_ctx* ctx, int ndim, const poms_layout* layout,
                              const int* p, const int* const* first, const int* const* es, const int* const* ee,
                              const double* const* basis, const double* const* weights, const int64_t* nglob,
                              const double* a_q, const double* c_q, double mass_coef, int64_t g0, poms_op** op);
+/* The same operator -div(a grad u) + c u WITHOUT a stored matrix (csrc/matfree.hip):
+ *   (A x)_i = sum_quadrature w [ c u_h phi_i + a grad u_h . grad phi_i ],
+ * evaluated, scaled and contracted per axis (sum factorisation) in one launch per
+ * call; the values at the quadrature points never reach device memory.  It stands for
+ * the matrix `assembly_2d` forms (`sources/matrix_assembler.py:84-179`) wherever only
+ * its product, diagonal and residual are needed, as in the cycle of
+ * `sources/mg_jac.py:84-119`.  The per-axis HOST tables are those of
+ * poms_op_assemble_stencil and are copied; a_q, c_q are DEVICE arrays over the global
+ * quadrature grid in the same order, or NULL for a = 1, c = mass_coef (then no array is
+ * read).  a_q and c_q are BORROWED, not copied: the caller keeps them alive and
+ * unchanged for the life of the handle.  The handle holds 8 B/DOF of its own, the
+ * diagonal sum_q w (c phi_i^2 + a |grad phi_i|^2), formed here once.  Every entry
+ * point that takes a general-stencil operator takes the result (apply, residual,
+ * Jacobi sweep with its sums, apply + dot, diag_scale, poms_pcg_jacobi), except
+ * poms_op_stencil_data and poms_op_galerkin_stencil; there is no two-sweeps-from-zero
+ * launch.  A launch allocates and synchronises nothing and can be the first call
+ * inside a stream capture; no atomics: two calls give the same bits.
+ * Checked before any device call (status 1 and a message): no null argument; ndim 2
+ * or 3; p[d] == layout->pads[d] in 1..3; nq[d] in 1..5; the whole grid (nglob ==
+ * layout->n, no POMS_LAYOUT_GHOST_DATA); every first / es / ee entry inside its range,
+ * non-decreasing and consistent (the kernel indexes with them unguarded); every
+ * tile's window within the kernel's limits.  A set-up call: it allocates, runs the
+ * diagonal kernel on the null stream and ends in a device synchronise.             */
+int poms_op_create_matfree(poms_ctx* ctx, int ndim, const poms_layout* layout, const int* nel, const int* nq,
+                           const int* p, const int* const* first, const int* const* es, const int* const* ee,
+                           const double* const* basis, const double* const* weights, const int64_t* nglob,
+                           const double* a_q, const double* c_q, double mass_coef, poms_op** op);
+/* diag(A) of the interior rows, dense C order, HOST output: the stored diagonal of a
+ * matrix-free operator, the centre coefficients of a general-stencil operator.   */
+int poms_op_diagonal(poms_op* op, double* diag_host);
 /* The coefficients of a general-stencil operator in the spl StencilMatrix._data
  * layout (the layout poms_op_create_stencil takes), HOST output.               */
 int poms_op_stencil_data(poms_op* op, double* data_host);

@@ -23,6 +23,7 @@ __all__ = [
     "QuadGrid", "PointGrid", "assemble_rhs", "evaluate", "l2_error",
     "SplinePoints", "Binning", "evaluate_at", "deposit",
     "galerkin_stencil", "GalerkinVCycle",
+    "MatrixFreeOperator", "MatrixFreeVCycle",
 ]
 
 
@@ -58,6 +59,9 @@ def __getattr__(name):
     if name in ("TwoLevelVCycle", "MultilevelVCycle", "GalerkinVCycle"):
         from . import mg
         return getattr(mg, name)
+    if name in ("MatrixFreeOperator", "MatrixFreeVCycle"):
+        from . import matfree
+        return getattr(matfree, name)
     if name == "SlabDistribution":
         from .dist import SlabDistribution
         return SlabDistribution

@@ -39,6 +39,15 @@ struct poms_op {
     poms::ToepConst tc{};
     double* coef = nullptr;   // FORM_STENCIL: (2p+1)^d coefficient planes of the owned rows
     int sp[3]{};              // FORM_STENCIL: stencil half-widths per axis
+    // FORM_MATFREE (poms_op_create_matfree): the per-axis device tables (owned, mf_tabs),
+    // the stored diagonal (dense C order, owned), the borrowed coefficient arrays at the
+    // quadrature points (null: a = 1, c = mf_mass) and the launch geometry
+    poms::AssembleAxis mf_ax[3]{};
+    std::vector<void*> mf_tabs;
+    double* mf_diag = nullptr;
+    const double *mf_a = nullptr, *mf_c = nullptr;
+    double mf_mass = 1.0;
+    poms::MatfreeGeom mf_geom{};
     uint64_t gen = 0;   // bumped by every setter that changes the launches a graph would capture
     // op_run_split's interior launch: the communication stream's exchange and boundary
     // launch run beside it (the automatic chunking leaves them CUs, op_geom); written
@@ -172,6 +181,10 @@ struct poms_ksolve {
     int* pivd[3]{};
     poms::BandLU f[3]{};
 };
+
+// the operator forms that run the general kernels (their own partials layout, no
+// two-sweeps-from-zero, a stored diagonal): the stored stencil and the matrix-free form
+inline bool general_form(const poms_op* o) { return o->form == poms::FORM_STENCIL || o->form == poms::FORM_MATFREE; }
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

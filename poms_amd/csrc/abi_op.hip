@@ -343,6 +343,153 @@ int poms_op_assemble_stencil(poms_ctx* ctx, int ndim, const poms_layout* layout,
     return 0;
 }
 
+// The matrix-free form of -div(a grad u) + c u (csrc/matfree.hip).  The kernel indexes
+// with the tables unguarded: every check comes first, before any device call.
+int poms_op_create_matfree(poms_ctx* ctx, int ndim, const poms_layout* layout, const int* nel, const int* nq,
+                           const int* p, const int* const* first, const int* const* es, const int* const* ee,
+                           const double* const* basis, const double* const* weights, const int64_t* nglob,
+                           const double* a_q, const double* c_q, double mass_coef, poms_op** op) {
+    const std::string fn = "poms_op_create_matfree: ";
+    if (!ctx || !op || !layout || !nel || !nq || !p || !first || !es || !ee || !basis || !weights || !nglob) {
+        set_error(fn + "null argument");
+        return 1;
+    }
+    if (ndim != 2 && ndim != 3) { set_error(fn + "ndim must be 2 or 3"); return 1; }
+    if (!layout_ok(layout)) { set_error(fn + "bad layout"); return 1; }
+    if (layout->flags & POMS_LAYOUT_GHOST_DATA) {
+        set_error(fn + "distributed operators (slabs, Cart blocks) are not supported");
+        return 1;
+    }
+    const int d0 = 3 - ndim;
+    for (int d = 0; d < d0; ++d)
+        if (layout->n[d] != 1 || layout->pads[d] != 0) { set_error(fn + "unused leading axes need n = 1, pads = 0"); return 1; }
+    const int T = matfree_tile();
+    for (int d = d0; d < 3; ++d) {
+        const std::string ax = "axis " + std::to_string(d) + ": ";
+        if (!first[d] || !es[d] || !ee[d] || !basis[d] || !weights[d]) { set_error(fn + ax + "null table"); return 1; }
+        if (p[d] < 1 || p[d] > 3) { set_error(fn + ax + "degree must be 1..3"); return 1; }
+        if (p[d] != layout->pads[d]) { set_error(fn + ax + "degree must equal the layout's pad"); return 1; }
+        if (nq[d] < 1 || nq[d] > 5) { set_error(fn + ax + "quadrature points per element must be 1..5"); return 1; }
+        if (nglob[d] != layout->n[d]) {
+            set_error(fn + ax + "distributed operators are not supported (nglob must equal the layout's extent)");
+            return 1;
+        }
+        const int64_t n = nglob[d];
+        if (n > 0x3fffffffLL || nel[d] < 1 || nel[d] > n) { set_error(fn + ax + "bad element count or extent"); return 1; }
+        const int ne = nel[d], pp = p[d];
+        for (int e = 0; e < ne; ++e)
+            if (first[d][e] < 0 || first[d][e] + pp >= n || (e > 0 && first[d][e] < first[d][e - 1])) {
+                set_error(fn + ax + "first[" + std::to_string(e) + "] outside its range or decreasing");
+                return 1;
+            }
+        for (int64_t i = 0; i < n; ++i) {
+            const int a = es[d][i], b = ee[d][i];
+            bool ok = a >= 0 && b < ne && a <= b && (i == 0 || (a >= es[d][i - 1] && b >= ee[d][i - 1]));
+            // every element of the support holds the function among its p+1
+            for (int e = a; ok && e <= b; ++e) ok = i >= first[d][e] && i <= first[d][e] + pp;
+            if (!ok) { set_error(fn + ax + "es / ee of basis function " + std::to_string(i) + " outside their range"); return 1; }
+        }
+        // every tile's window and element range fit the kernel's LDS arrays
+        for (int64_t lo = 0; lo < n; lo += T) {
+            const int64_t hi = std::min<int64_t>(lo + T, n);
+            const int ea = es[d][lo], eb = ee[d][hi - 1];
+            if (eb - ea + 1 > matfree_max_elements() || first[d][eb] + pp + 1 - first[d][ea] > matfree_max_window()) {
+                set_error(fn + ax + "a tile's element range or window exceeds the kernel's limits");
+                return 1;
+            }
+        }
+    }
+    const int64_t ndof = layout->n[0] * layout->n[1] * layout->n[2];
+    if (ndof > ((int64_t)1 << 36)) { set_error(fn + "grid too large"); return 1; }
+    POMS_HIP_CHECK(hipSetDevice(ctx->device));
+    const RowGeom r = row_geom(layout);
+    auto* o = new poms_op();
+    o->ctx = ctx;
+    o->ndim = ndim;
+    o->form = FORM_MATFREE;
+    o->pmax = std::max(r.pd0, std::max(r.pd1, r.pd2));
+    o->L = *layout;
+    o->g0 = 0;
+    o->n0g = ndim == 3 ? nglob[0] : 1;
+    o->sp[0] = r.pd0; o->sp[1] = r.pd1; o->sp[2] = r.pd2;
+    o->mf_a = a_q;
+    o->mf_c = c_q;
+    o->mf_mass = mass_coef;
+    auto up = [&](const void* h, size_t bytes) -> void* {
+        void* d = nullptr;
+        if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
+        o->mf_tabs.push_back(d);
+        if (hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        return d;
+    };
+    static const int zero_i = 0;
+    static const double unit_b[2] = {1.0, 0.0}, unit_w = 1.0;
+    int rc = 0;
+    for (int d = 0; d < 3 && !rc; ++d) {
+        const bool used = d >= d0;
+        const int ne = used ? nel[d] : 1, q = used ? nq[d] : 1, pp = used ? p[d] : 0;
+        const int64_t n = used ? nglob[d] : 1;
+        AssembleAxis& A = o->mf_ax[d];
+        A.first = static_cast<const int*>(up(used ? first[d] : &zero_i, ne * sizeof(int)));
+        A.es = static_cast<const int*>(up(used ? es[d] : &zero_i, n * sizeof(int)));
+        A.ee = static_cast<const int*>(up(used ? ee[d] : &zero_i, n * sizeof(int)));
+        A.basis = static_cast<const double*>(up(used ? basis[d] : unit_b, (size_t)ne * q * (pp + 1) * 2 * sizeof(double)));
+        A.w = static_cast<const double*>(up(used ? weights[d] : &unit_w, (size_t)ne * q * sizeof(double)));
+        A.nel = ne; A.nq = q; A.p = pp; A.n = (int)n;
+        if (!A.first || !A.es || !A.ee || !A.basis || !A.w) rc = 1;
+    }
+    if (!rc && hipMalloc(reinterpret_cast<void**>(&o->mf_diag), std::max<int64_t>(ndof, 1) * sizeof(double)) != hipSuccess)
+        rc = 1;
+    if (!rc) {
+        matfree_diag_launch(o->mf_ax, a_q, c_q, mass_coef, o->mf_diag, nullptr);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = 1;
+    }
+    if (rc) {
+        set_error(fn + "allocation, upload or launch failed");
+        poms_op_destroy(o);
+        return 1;
+    }
+    // launch geometry: 3D marches chunks of axis 0, at least 16 planes each; the number
+    // of chunks with the fewest plane steps over whole rounds of the 512 workgroups the
+    // 256 CUs hold (two per CU at 63 KB of LDS each), a chunk costing its planes + p0
+    MatfreeGeom& g = o->mf_geom;
+    g.s0 = r.s0; g.s1 = r.s1;
+    g.n0 = r.n0; g.n1 = r.n1; g.n2 = r.n2;
+    g.pd0 = r.pd0; g.pd1 = r.pd1; g.pd2 = r.pd2;
+    g.tiles1 = (r.n1 + T - 1) / T;
+    g.tiles2 = (r.n2 + T - 1) / T;
+    const int64_t t12 = (int64_t)g.tiles1 * g.tiles2;
+    int64_t want = 1;
+    double best = 1e300;
+    for (int64_t nc = 1; nc <= std::max(1, r.n0 / 16); ++nc) {
+        const double cost = (double)((t12 * nc + 511) / 512) * (double)((r.n0 + nc - 1) / nc + r.pd0);
+        if (cost < best - 1e-9) { best = cost; want = nc; }
+    }
+    g.chunk = (int)((r.n0 + want - 1) / want);
+    g.nchunks = (r.n0 + g.chunk - 1) / g.chunk;
+    g.ntiles = t12 * g.nchunks;
+    *op = o;
+    return 0;
+}
+
+int poms_op_diagonal(poms_op* o, double* diag_host) {
+    if (!o || !diag_host) { set_error("poms_op_diagonal: null argument"); return 1; }
+    const RowGeom r = row_geom(&o->L);
+    const int64_t cst = (int64_t)r.n0 * r.n1 * r.n2;
+    const double* src = nullptr;
+    if (o->form == FORM_MATFREE) {
+        src = o->mf_diag;
+    } else if (o->form == FORM_STENCIL && o->coef) {   // the centre offset's coefficient plane
+        const int w1 = 2 * o->sp[1] + 1, w2 = 2 * o->sp[2] + 1;
+        src = o->coef + ((int64_t)(o->sp[0] * w1 + o->sp[1]) * w2 + o->sp[2]) * cst;
+    } else {
+        set_error("poms_op_diagonal: needs a matrix-free or general-stencil operator");
+        return 1;
+    }
+    POMS_HIP_CHECK(hipMemcpy(diag_host, src, cst * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int poms_op_stencil_data(poms_op* o, double* data_host) {
     if (!o || !data_host || o->form != FORM_STENCIL) { set_error("poms_op_stencil_data: needs a general-stencil operator"); return 1; }
     const RowGeom r = row_geom(&o->L);
@@ -511,6 +658,9 @@ int poms_op_destroy(poms_op* o) {
     for (double* p : {o->a0t, o->b0t, o->a1, o->b1, o->a2, o->b2, o->dg2a, o->dg2b, o->rdiag0, o->coef, o->sv_dev,
                       o->spec_dev, o->spec_bak, o->la_raw})
         if (p) (void)hipFree(p);
+    for (void* p : o->mf_tabs)
+        if (p) (void)hipFree(p);
+    if (o->mf_diag) (void)hipFree(o->mf_diag);
     for (double* p : {o->sv_host, o->sv_part, o->spec_part, o->spec_host})
         if (p) (void)hipHostFree(p);
     for (auto& g : o->spec_graphs)
@@ -720,7 +870,7 @@ static int op_geom(poms_op* o, int64_t zb, int64_t ze, KronGeom& g, int v = -1, 
 
 // variants whose Jacobi epilogue also accumulates x_out . b (v3 and v4 kernels)
 static bool fused_dot_ok(const poms_op* o) {
-    return o->form == FORM_STENCIL || (o->variant >= 4 && o->variant <= 10) || o->variant == 114;
+    return general_form(o) || (o->variant >= 4 && o->variant <= 10) || o->variant == 114;
 }
 
 
@@ -745,6 +895,42 @@ static int stencil_run(poms_op* o, int epi, double omega, const double* x, doubl
         return 1;
     POMS_HIP_CHECK(hipGetLastError());
     o->last_partials = red ? nb : 0;
+    return 0;
+}
+
+// Matrix-free launch (FORM_MATFREE): stencil_run's epilogues and partials layout
+// (norms at scratch[0, nb), dots behind them).  The whole grid in one launch: the
+// operator is undistributed, so the plane range must be all of axis 0.  Nothing is
+// allocated or synchronised here.
+static int matfree_run(poms_op* o, int epi, double omega, const double* x, double* y, const double* b,
+                       int64_t zb, int64_t ze, int want_norm, void* stream, int want_dot, int64_t zb2,
+                       int64_t ze2) {
+    if (epi == EPI_JACOBI0) { set_error("matrix-free operator: no two-sweeps-from-zero epilogue"); return 1; }
+    if (want_dot && epi != EPI_JACOBI && epi != EPI_APPLYDOT) { set_error("matrix-free operator: dot needs Jacobi / apply+dot"); return 1; }
+    const RowGeom r = row_geom(&o->L);
+    if (zb != 0 || ze != r.n0 || zb2 != ze2) { set_error("matrix-free operator: the plane range must be the whole axis 0"); return 1; }
+    const int maxb = (int)(kScratch / 2);
+    double* scr = o->ctx->scratch;
+    int nb = 0;
+    if (epi == EPI_DIAG) {   // x = scale b / diag: the general stencil's kernel on the stored diagonal
+        StencilGeom g{r.s0, r.s1, r.n0, r.n1, r.n2, r.pd0, r.pd1, r.pd2, 0, 0, 0, 1, 1, 1,
+                      (int64_t)r.n0 * r.n1 * r.n2, 0, r.n0, 0, 0};
+        if (stencil_launch(EPI_DIAG, g, o->mf_diag, x, y, b, omega, want_norm ? scr : nullptr, nullptr, maxb,
+                           as_stream(stream), &nb))
+            return 1;
+        POMS_HIP_CHECK(hipGetLastError());
+        o->last_partials = want_norm ? nb : 0;
+        return 0;
+    }
+    if ((epi == EPI_JACOBI || epi == EPI_APPLYDOT) && x == y) { set_error("matrix-free operator: y must not alias x"); return 1; }
+    const MatfreeGeom& g = o->mf_geom;
+    const int nblk = (int)std::min<int64_t>(g.ntiles, maxb);
+    const bool wd = want_dot || epi == EPI_APPLYDOT;
+    if (matfree_launch(epi, g, o->mf_ax, x, y, b, o->mf_a, o->mf_c, o->mf_diag, o->mf_mass, omega,
+                       want_norm ? scr : nullptr, wd ? scr + nblk : nullptr, maxb, as_stream(stream), &nb))
+        return 1;
+    POMS_HIP_CHECK(hipGetLastError());
+    o->last_partials = (want_norm || wd) ? nb : 0;
     return 0;
 }
 
@@ -797,7 +983,7 @@ static int resolve_variant(const poms_op* o, int epi) {
 // Kronecker operators whose single sweep runs the v3 whole-array kernel (variant 9),
 // whose bits the two-sweep kernel reproduces
 bool poms::sweep2_ok(const poms_op* o) {
-    if (o->ndim != 2 || o->pmax != 3 || o->form == FORM_STENCIL || o->ghost_corners) return false;
+    if (o->ndim != 2 || o->pmax != 3 || general_form(o) || o->ghost_corners) return false;
     if (o->L.pads[1] != 3 || o->L.pads[2] != 3 || resolve_variant(o, EPI_JACOBI) != 9) return false;
     const int64_t bytes = (int64_t)(o->L.n[0] + 2 * o->L.pads[0]) * row_geom(&o->L).s0 * 8;
     return bytes < 0x7ffffff0LL;
@@ -873,6 +1059,8 @@ static int op_run(poms_op* o, int epi, double omega, const double* x, double* y,
     if (epi == EPI_JACOBI2 || epi == EPI_JACOBI3Z) return op_run_j2(o, epi, omega, x, y, b, want_norm, want_dot, stream);
     if (o->form == FORM_STENCIL)
         return stencil_run(o, epi, omega, x, y, b, zb, ze, want_norm, stream, want_dot, zb2, ze2);
+    if (o->form == FORM_MATFREE)
+        return matfree_run(o, epi, omega, x, y, b, zb, ze, want_norm, stream, want_dot, zb2, ze2);
     if (epi == EPI_APPLYDOT && !(o->variant == 4 || o->variant == 8 || o->variant == 9 || o->variant == 10)) {
         set_error("apply + x.y: kernel variants 4, 8, 9, 10 only");
         return 1;
@@ -992,7 +1180,7 @@ int poms_op_apply_dot(poms_op* op, const double* x, double* y, int64_t zb, int64
 int poms_op_apply_dot_supported(poms_op* op, int* yes) {
     if (!op || !yes) { set_error("poms_op_apply_dot_supported: null argument"); return 1; }
     const int v = op->variant;
-    *yes = (op->form == FORM_STENCIL || v == 4 || v == 8 || v == 9 || v == 10) ? 1 : 0;
+    *yes = (general_form(op) || v == 4 || v == 8 || v == 9 || v == 10) ? 1 : 0;
     return 0;
 }
 
@@ -1011,7 +1199,7 @@ int poms_op_from_zero_supported(poms_op* op, int* yes) {
     const int64_t bytes = (int64_t)(op->L.n[0] + 2 * op->L.pads[0]) * row_geom(&op->L).s0 * 8;
     // 2D (round 6, v3): not on a block of a decomposition (its ghost rows' x1 would need
     // the neighbours' diagonal)
-    *yes = ((op->ndim == 3 || (op->ndim == 2 && !op->ghost_corners)) && op->form != FORM_STENCIL &&
+    *yes = ((op->ndim == 3 || (op->ndim == 2 && !op->ghost_corners)) && !general_form(op) &&
             (op->variant == 8 || op->variant == 9 || op->variant == 10 ||
              (op->variant >= 110 && op->variant <= 112) || op->variant == 114) &&
             bytes < 0x7ffffff0LL) ? 1 : 0;
@@ -1051,6 +1239,8 @@ int poms_op_diag_scale(poms_op* o, double scale, const double* b, double* x, int
     if (!o || !b || !x) { set_error("poms_op_diag_scale: null argument"); return 1; }
     if (o->form == FORM_STENCIL)
         return stencil_run(o, EPI_DIAG, scale, b, x, b, 0, o->L.n[0], want_norm, stream, 0, 0, 0);
+    if (o->form == FORM_MATFREE)
+        return matfree_run(o, EPI_DIAG, scale, b, x, b, 0, o->L.n[0], want_norm, stream, 0, 0, 0);
     const RowGeom g = row_geom(&o->L);
     int nb = 0;
     diag_scale_launch(o->ndim == 3, o->form, g, o->pmax, (int)o->g0, scale, b, x, o->a0t, o->b0t,
@@ -1134,7 +1324,7 @@ int op_run_split(poms_op* op, int epilogue, double omega, const double* x, doubl
                  int64_t ib, int64_t ie, int64_t b1s, int64_t b1e, int64_t b2s, int64_t b2e, double* norm_out,
                  double* dot_out, const SplitHooks& h, void* stream) {
     if (!op) { set_error("op_run_split: null operator"); return 1; }
-    if (op->form == FORM_STENCIL) {   // its own partials layout: reduce each launch, both on `stream`
+    if (general_form(op)) {   // its own partials layout: reduce each launch, both on `stream`
         if (poms_op_run_reduce2(op, epilogue, omega, x, y, b, ib, ie, 0, 0, norm_out, dot_out, 0, stream)) return 1;
         if (h.ghosts_on(h.arg, stream)) return 1;
         return poms_op_run_reduce2(op, epilogue, omega, x, y, b, b1s, b1e, b2s, b2e, norm_out, dot_out, 1, stream);

@@ -11,7 +11,8 @@ constexpr int kBlock = 256;  // 4 wave64s per workgroup
 // that writes per-block partials there caps its grid at this (vec_ops.hip asserts it)
 constexpr int64_t kScratch = 1 << 16;
 
-enum Form : int { FORM_SINGLE = 0, FORM_SUM = 1, FORM_STENCIL = 2 };
+enum Form : int { FORM_SINGLE = 0, FORM_SUM = 1, FORM_STENCIL = 2,
+                  FORM_MATFREE = 3 /* quadrature form applied without a stored matrix (matfree.hip) */ };
 enum Epi : int { EPI_APPLY = 0, EPI_RESID = 1, EPI_JACOBI = 2,
                  EPI_JACOBI0 = 3,   /* two damped-Jacobi sweeps from x0 = 0 (x planes = b) */
                  EPI_APPLYDOT = 4,  /* y = A x and per-block sums of x . y              */
@@ -67,6 +68,16 @@ struct AssembleAxis {
     const double* basis;   // nel*nq*(p+1)*2: value, derivative
     const double* w;       // nel*nq: quadrature weights (with the element Jacobian)
     int nel, nq, p, n;
+};
+
+// One launch of the matrix-free operator (matfree.hip): tiles of matfree_tile() output
+// columns on axes 1 and 2, chunks of `chunk` output planes on axis 0.
+struct MatfreeGeom {
+    int64_t s0, s1;          // plane / row strides of the padded vectors
+    int n0, n1, n2;          // interior extents (the whole grid)
+    int pd0, pd1, pd2;       // storage pads
+    int tiles1, tiles2, nchunks, chunk;
+    int64_t ntiles;          // tiles1 tiles2 nchunks
 };
 
 // pcg's scalars folded into the flat vector updates (one rank, round 6): every block

@@ -60,6 +60,16 @@ int stencil_launch(int epi, const StencilGeom& g, const double* coef, const doub
                    const double* b, double omega, double* partial, double* partial2, int max_blocks,
                    hipStream_t st, int* nblk_out);
 
+// ---- matfree.hip ------------------------------------------------------------------
+int matfree_tile();           // output columns per tile edge (axes 1, 2)
+int matfree_max_window();     // widest x window a tile may need per axis
+int matfree_max_elements();   // most elements a tile may touch per axis
+int matfree_diag_launch(const AssembleAxis* ax, const double* a_q, const double* c_q, double mass_coef, double* diag,
+                        hipStream_t st);
+int matfree_launch(int epi, const MatfreeGeom& g, const AssembleAxis* ax, const double* x, double* y, const double* b,
+                   const double* a_q, const double* c_q, const double* diag, double mass_coef, double omega,
+                   double* partial, double* partial2, int max_blocks, hipStream_t st, int* nblk_out);
+
 // ---- stencil_galerkin.hip ---------------------------------------------------------
 // One axis of the Galerkin product P^T A P of a general stencil: coefficient planes
 // [k0][k1][k2] of rows nin -> nout (they differ on axis d only).  Column I of P_d has

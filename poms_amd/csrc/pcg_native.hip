@@ -101,7 +101,7 @@ struct PcgRun {
     }
     // q = A p, p.q and alpha: one rank folds p.q's reduction into the alpha kernel
     int apd_alpha(const double* p, double* q) {
-        if (comm || op->dot_base >= 0 || op->part_off != 0 || op->part_dst || op->form == FORM_STENCIL) {
+        if (comm || op->dot_base >= 0 || op->part_off != 0 || op->part_dst || general_form(op)) {
             if (run(EPI_APPLYDOT, p, q, p, nullptr, sc + SC_PQ) || allsum(sc + SC_PQ, 1)) return 1;
             hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, st, sc, 0);
             POMS_HIP_CHECK(hipGetLastError());
@@ -425,7 +425,7 @@ struct PcgRun {
         return lazy_post(h, 1);
     }
     int diag_scale_norm(const double* b, double* x, int h) {   // x = omega b / diag, ||x||^2 -> host slot h
-        if (direct() && op->form != FORM_STENCIL) {   // partials straight into slot h's host region
+        if (direct() && !general_form(op)) {   // partials straight into slot h's host region
             const RowGeom g = row_geom(&op->L);
             const int nb = diag_scale_blocks(op->ndim == 3, g);
             if (nb <= host_partials_max()) {
@@ -495,7 +495,7 @@ struct PcgRun {
         const int maxit = o->jmaxiter;
         double *x = A, *xn = B;
         int fz = 0, k0;
-        if (maxit >= 2 && maxit != 2 && op->form != FORM_STENCIL) (void)poms_op_from_zero_supported(op, &fz);
+        if (maxit >= 2 && maxit != 2 && !general_form(op)) (void)poms_op_from_zero_supported(op, &fz);
         if (fz) {   // sweeps 1, 2 from x = 0: [||x1||^2, ||dr2||^2]
             int vi;
             if (sjrun(EPI_JACOBI0, rhs, A, rhs, true, true, &vi)) return 1;
@@ -546,7 +546,7 @@ struct PcgRun {
                                                   // 5: sweeps 1-3 from zero
         int nq = 0, ring = 0, k0;
         int fz = 0;
-        if (maxit >= 2 && maxit != 2 && op->form != FORM_STENCIL) (void)poms_op_from_zero_supported(op, &fz);
+        if (maxit >= 2 && maxit != 2 && !general_form(op)) (void)poms_op_from_zero_supported(op, &fz);
         // sweeps 1-3 from x = 0 in one launch where the two-sweep launches run (POMS_J2FZ=0: off)
         static const bool j3_env = !(getenv("POMS_J2FZ") && getenv("POMS_J2FZ")[0] == '0');
         if (fz && j2 && j3_env && maxit >= 4) {   // [||x1||^2, ||dr2||^2, ||dr3||^2]
@@ -641,7 +641,7 @@ struct PcgRun {
             if (last) {   // the last sweep's norm cannot change the result: x . rhs instead
                 dot_part_n = -1;
                 if (direct() && dot_idx == SC_SRN && op->dot_base < 0 && op->part_off == 0 && !op->part_dst &&
-                    op->form != FORM_STENCIL) {   // its partials wait for pcg_beta_kernel
+                    !general_form(op)) {   // its partials wait for pcg_beta_kernel
                     if (op_run_epi(op, EPI_JACOBI, o->omega, bufs[cur], bufs[nxt], rhs, 0, n0, 0, 0, false, true, stv))
                         return 1;
                     dot_part_n = op->last_partials;

@@ -1,0 +1,216 @@
+"""Matrix-free variable-coefficient operator and its V-cycle.
+
+``-∇·(a∇u) + c u`` on a tensor B-spline space applied without a stored matrix
+(``csrc/matfree.hip``, ``poms_op_create_matfree``):
+
+    (A x)_i = Σ_q w_q [ c(q) u_h(q) φ_i(q) + a(q) ∇u_h(q)·∇φ_i(q) ]
+
+is an evaluation at the quadrature points, a pointwise scaling and a load-vector
+contraction, fused in one kernel.  It is the operator the reference assembles in
+``assembly_2d`` (`sources/matrix_assembler.py:84-179`); its cycle
+(`sources/mg_jac.py:84-119`) needs the fine operator only as ``A.dot``, its diagonal and
+the residual.  Where :func:`~poms_amd.assembly.assemble_stencil` stores ``(2p+1)^d``
+coefficients per row (2744 B/DOF in 3D at p = 3) this form holds the two coefficient
+arrays at the quadrature points and an 8 B/DOF diagonal.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .assembly import _coef_field, assemble_stencil, axis_tables
+from .mg import GalerkinVCycle, two_level_setup_1d
+from .splines import uniform_knots
+from .stencil import KronOperator, StencilVectorSpace
+
+
+def _coef_arg(f, tabs, device):
+    """A coefficient as the device array the operator borrows: None stays None; a
+    float64 device tensor of the quadrature grid's shape is used in place; a scalar, an
+    array or a callable goes through :func:`assemble_stencil`'s preparation."""
+    shape = tuple(t["nel"] * t["nq"] for t in tabs)
+    if f is None:
+        return None
+    if isinstance(f, torch.Tensor):
+        if f.dtype != torch.float64:
+            raise TypeError(f"coefficient tensor must be float64, got {f.dtype}")
+        if tuple(f.shape) != shape:
+            raise ValueError(f"coefficient tensor has shape {tuple(f.shape)}, the quadrature grid {shape}")
+        if f.device != torch.device(device):
+            raise ValueError(f"coefficient tensor lives on {f.device}, the space on {device}")
+        if not f.is_contiguous():
+            raise ValueError("coefficient tensor must be contiguous (C order)")
+        return f
+    if not callable(f):
+        got = np.shape(f)
+        if got != () and got != shape:
+            raise ValueError(f"coefficient array has shape {got}, the quadrature grid {shape}")
+    return _coef_field(f, tabs, device)
+
+
+class MatrixFreeOperator(KronOperator):
+    """``-∇·(a∇u) + c u`` on the tensor space of ``knots`` (degree = the space's pads,
+    1…3; ``nquad`` 1…5 Gauss points per element, default ``p+1``), applied matrix-free.
+
+    ``a`` / ``c``: what :func:`~poms_amd.assembly.assemble_stencil` accepts (None for 1
+    and ``mass_coef``, a scalar, an array of the quadrature grid's shape
+    (:attr:`quad_shape`), a NumPy callable of the ``meshgrid`` coordinates), or a
+    float64 device tensor of that shape, which is used in place without a copy: the
+    operator keeps a reference, and later changes to the tensor change the operator
+    (but not its diagonal, formed once at creation).
+
+    ``dot``, ``residual``, ``dot_inner``, ``jacobi_sweep`` and ``diag_scale`` run the
+    kernel's epilogues; ``pcg``, ``damped_jacobi``, ``jacobi`` and ``crl`` take the
+    operator unchanged.  :meth:`assemble` gives the stored stencil of the same
+    arguments for cross-checks."""
+
+    def __init__(self, V: StencilVectorSpace, knots, a=None, c=None, mass_coef: float = 1.0,
+                 nquad: int | None = None):
+        if V.is_cart or V.is_distributed or tuple(V.local_npts) != tuple(V.npts):
+            raise NotImplementedError("matrix-free operators are implemented for undistributed spaces "
+                                      "(no slab or Cart decomposition)")
+        nd = V.ndim
+        if nd not in (2, 3):
+            raise ValueError("matrix-free operators are 2D or 3D")
+        if len(knots) != nd:
+            raise ValueError(f"{nd}D space needs {nd} knot vectors")
+        tabs = [axis_tables(np.asarray(T, float), V.pads[d], nquad) for d, T in enumerate(knots)]
+        for d, t in enumerate(tabs):
+            if t["n"] != V.npts[d]:
+                raise ValueError(f"axis {d}: knots give {t['n']} basis functions, space has {V.npts[d]}")
+        self.space, self.form = V, "matfree"
+        self.pmax = max(max(V.pads), 1)
+        self.bands, self.timer, self._calls = {}, None, 0
+        self._h = C.c_void_p()
+        self.pads, self.starts, self.ends = V.pads, V.starts, V.ends
+        self.knots = [np.asarray(T, float).copy() for T in knots]
+        self.nquad, self.mass_coef = nquad, float(mass_coef)
+        self._args = (a, c)
+        self.quad_shape = tuple(t["nel"] * t["nq"] for t in tabs)
+        dev = f"cuda:{V.device}"
+        # the arrays the handle borrows live as long as this object
+        self._aq, self._cq = _coef_arg(a, tabs, dev), _coef_arg(c, tabs, dev)
+        self._diag = None
+        lead = 3 - nd
+        keep = []
+
+        def arr3(key, np_dtype):
+            out = (C.c_void_p * 3)()
+            for k, t in enumerate(tabs):
+                a_ = np.ascontiguousarray(t[key], dtype=np_dtype)
+                keep.append(a_)
+                out[lead + k] = a_.ctypes.data
+            return out
+
+        ints = lambda key: [0] * lead + [int(t[key]) for t in tabs]
+        nel, nq, pp = (C.c_int * 3)(*ints("nel")), (C.c_int * 3)(*ints("nq")), (C.c_int * 3)(*ints("p"))
+        nglob = (C.c_int64 * 3)(*([1] * lead + [int(t["n"]) for t in tabs]))
+        try:
+            _lib.call("poms_op_create_matfree", V.ctx, nd, C.byref(V.layout), nel, nq, pp,
+                      arr3("first", np.int32), arr3("es", np.int32), arr3("ee", np.int32),
+                      arr3("basis", np.float64), arr3("weights", np.float64), nglob,
+                      None if self._aq is None else C.c_void_p(self._aq.data_ptr()),
+                      None if self._cq is None else C.c_void_p(self._cq.data_ptr()),
+                      self.mass_coef, C.byref(self._h))
+        except _lib.PomsError as e:
+            raise ValueError(str(e)) from None
+
+    def diagonal(self) -> torch.Tensor:
+        """diag(A) of the interior rows as a device tensor of the grid's shape (the
+        stored diagonal ``Σ_q w (c φ_i² + a |∇φ_i|²)`` the Jacobi epilogue divides by)."""
+        if self._diag is None:
+            V = self.space
+            host = np.empty(V.npts)
+            _lib.call("poms_op_diagonal", self._h, host.ctypes.data_as(C.c_void_p))
+            self._diag = torch.from_numpy(host).to(f"cuda:{V.device}")
+        return self._diag
+
+    def device_bytes(self) -> int:
+        """Bytes of device memory the operator holds (coefficient arrays, diagonal)."""
+        n = int(np.prod(self.space.npts)) * 8
+        for t in (self._aq, self._cq):
+            if t is not None:
+                n += t.numel() * 8
+        return n
+
+    def assemble(self):
+        """The stored stencil :func:`~poms_amd.assembly.assemble_stencil` forms from the
+        same arguments (for cross-checks and host-side views)."""
+        a, c = self._args
+        to_np = lambda f: f.cpu().numpy() if isinstance(f, torch.Tensor) else f
+        return assemble_stencil(self.space, self.knots, a=to_np(a), c=to_np(c), mass_coef=self.mass_coef,
+                                nquad=self.nquad)
+
+    def _no_matrix(self, what):
+        raise NotImplementedError(f"a matrix-free operator stores no coefficients: {what} is not available; "
+                                  "use .assemble() for the stored stencil of the same arguments")
+
+    def tosparse(self):
+        self._no_matrix("tosparse()")
+
+    def tocsr(self):
+        self._no_matrix("tocsr()")
+
+    def toarray(self):
+        self._no_matrix("toarray()")
+
+    def __getitem__(self, key):
+        self._no_matrix("element access")
+
+    def diagonal_axes(self):
+        raise NotImplementedError("a matrix-free operator has no per-axis factors; use .diagonal()")
+
+
+class MatrixFreeVCycle(GalerkinVCycle):
+    """:class:`~poms_amd.mg.GalerkinVCycle`'s cycle with a matrix-free finest level:
+    ``ops[0]`` is a :class:`MatrixFreeOperator`, ``ops[1]`` the stencil assembled on
+    level 1's knots, ``ops[l ≥ 2] = galerkin_stencil(ops[l-1], P[l-1])``, and the
+    coarsest level is inverted densely.  The sequence of a level is
+    ``GalerkinVCycle._level``, unchanged.
+
+    Level 1 is a *rediscretisation*, not a Galerkin product: it equals ``PᵀA₀P``
+    exactly when ``a`` and ``c`` are integrated exactly on both levels (polynomials of
+    degree ≤ 1 per axis at ``nquad = p+1``), and to quadrature accuracy otherwise.
+    Below level 1 the coarse operators are Galerkin products of it.
+
+    ``A``: the finest operator; ``P[l]``: the 1D prolongations from level ``l+1`` to
+    ``l``; ``A1``: the level-1 :class:`~poms_amd.stencil.StencilMatrix` (on the space
+    of ``P[0]``'s columns)."""
+
+    def __init__(self, A: MatrixFreeOperator, P, A1, *, tol: float = 1e-6, maxiters=None):
+        if tuple(A1.space.npts) != tuple(np.shape(p)[1] for p in P[0]):
+            raise ValueError("the level-1 operator does not live on the columns of P[0]")
+        self._A1 = A1
+        super().__init__(A, P, tol=tol, maxiters=maxiters)
+
+    def _coarse_op(self, l: int):
+        return self._A1 if l == 0 else super()._coarse_op(l)
+
+    @classmethod
+    def uniform(cls, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *, a=None, c=None,
+                mass_coef: float = 1.0, nquad: int | None = None, device=None, tol: float = 1e-6, maxiters=None):
+        """Dyadic uniform hierarchy, as :meth:`GalerkinVCycle.uniform`.  ``a`` / ``c``:
+        None, scalars or callables (they are sampled on two quadrature grids, the
+        finest level's and level 1's)."""
+        for f in (a, c):
+            if f is not None and not callable(f) and np.ndim(f) != 0:
+                raise ValueError("a / c must be None, scalars or callables here: they are sampled on two grids")
+        if ncells_fine < ncells_coarsest or ncells_coarsest < 1:
+            raise ValueError("need ncells_fine >= ncells_coarsest >= 1")
+        cells = [int(ncells_fine)]
+        while cells[-1] // 2 >= ncells_coarsest and cells[-1] % 2 == 0:
+            cells.append(cells[-1] // 2)
+        if len(cells) < 2:
+            raise ValueError("the hierarchy needs at least two levels (even cell counts)")
+        knots = [uniform_knots(p, N) for N in cells]
+        P1 = [two_level_setup_1d(p, knots[l], knots[l + 1])[2] for l in range(len(cells) - 1)]
+        V = StencilVectorSpace([len(knots[0]) - p - 1] * ndim, [p] * ndim, device=device, align=True)
+        A = MatrixFreeOperator(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef, nquad=nquad)
+        V1 = StencilVectorSpace([len(knots[1]) - p - 1] * ndim, [p] * ndim, device=V.device, align=True)
+        A1 = assemble_stencil(V1, [knots[1]] * ndim, a=a, c=c, mass_coef=mass_coef, nquad=nquad)
+        mg = cls(A, [[P1l] * ndim for P1l in P1], A1, tol=tol, maxiters=maxiters)
+        mg.p, mg.ndim, mg.cells, mg.knots, mg.P1 = int(p), int(ndim), cells, knots, P1
+        return mg

@@ -304,7 +304,6 @@ class GalerkinVCycle:
     """
 
     def __init__(self, A, P, *, tol: float = 1e-6, maxiters=None):
-        from .multilevels import galerkin_stencil
         if len(P) < 1:
             raise ValueError("the hierarchy needs at least two levels")
         self.tol = tol
@@ -315,7 +314,7 @@ class GalerkinVCycle:
         self.P = [[np.ascontiguousarray(p, dtype=np.float64) for p in Pl] for Pl in P]
         self.ops, self.spaces, self.transfers = [A], [A.space], []
         for l in range(L - 1):
-            Ac = galerkin_stencil(self.ops[l], self.P[l])
+            Ac = self._coarse_op(l)
             self.transfers.append(KronTransfer(self.spaces[l], self.P[l]))
             self.ops.append(Ac)
             self.spaces.append(Ac.space)
@@ -328,6 +327,11 @@ class GalerkinVCycle:
         self.rcs = [torch.empty(tr.ncoarse, dtype=F64, device=dev) for tr in self.transfers]
         self.xc = torch.empty(Ac.shape[0], dtype=F64, device=dev)
         self.infos = [None] * (L - 1)
+
+    def _coarse_op(self, l: int):
+        """Level ``l+1``'s operator from level ``l``'s (subclasses may rediscretise)."""
+        from .multilevels import galerkin_stencil
+        return galerkin_stencil(self.ops[l], self.P[l])
 
     @classmethod
     def uniform(cls, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *, a=None, c=None,
