@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define POMS_ABI_VERSION 5 /* 5: poms_op_create_matfree, poms_op_diagonal */
+#define POMS_ABI_VERSION 6 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor */
 
 /* operator forms (see poms_op_create) */
 #define POMS_FORM_SINGLE 0 /* y = F0 (x) F1 (x) F2 x                                  */
@@ -146,6 +146,34 @@ int poms_op_create_matfree(poms_ctx* ctx, int ndim, const poms_layout* layout, c
                            const int* p, const int* const* first, const int* const* es, const int* const* ee,
                            const double* const* basis, const double* const* weights, const int64_t* nglob,
                            const double* a_q, const double* c_q, double mass_coef, poms_op** op);
+/* Tensor coefficients: -div(G grad u) + c u with a full symmetric tensor G at the
+ * quadrature points,
+ *   M[i, j] = sum_quadrature w (c phi_i phi_j + grad phi_i^T G grad phi_j),
+ * all d^2 gradient products.  This is the call `assembly_2d`
+ * (`sources/matrix_assembler.py:84-179`) makes, generalised from the unit square to a
+ * mapped domain x = F(xi): there G = a |det J| J^-1 J^-T and c = c |det J| with
+ * J = dF/dxi; anisotropic diffusion is the same operator.  The arguments are those of
+ * poms_op_assemble_stencil with a_q replaced by (g_q, ncomp): g_q is one contiguous
+ * DEVICE array of shape (ncomp, Q0, Q1, Q2) over the global quadrature grid (2D:
+ * (ncomp, Q1, Q2)), ncomp = d (d + 1) / 2 component planes, the upper triangle in
+ * row-major order of the operator's axes (3D: 00 01 02 11 12 22; 2D: 00 01 11 of the 2D
+ * operator).  g_q must not be NULL; ncomp must equal d (d + 1) / 2.  The scalar
+ * operator of a is the tensor a I up to rounding.                                  */
+int poms_op_assemble_stencil_tensor(poms_ctx* ctx, int ndim, const poms_layout* layout, const int* nel, const int* nq,
+                                    const int* p, const int* const* first, const int* const* es,
+                                    const int* const* ee, const double* const* basis, const double* const* weights,
+                                    const int64_t* nglob, const double* g_q, int ncomp, const double* c_q,
+                                    double mass_coef, int64_t g0, poms_op** op);
+/* The matrix-free form of the tensor operator: poms_op_create_matfree with a_q replaced
+ * by (g_q, ncomp) as above, for the matrix `assembly_2d` would form on a mapped domain
+ * (`sources/matrix_assembler.py:84-179`).  g_q is BORROWED like a_q and c_q.  Every
+ * check of poms_op_create_matfree applies, and g_q != NULL, ncomp == d (d + 1) / 2.  The
+ * call also reads the tensor kernels' attributes and refuses, with a message, a build
+ * that spills to scratch (it would no longer run two workgroups per CU).           */
+int poms_op_create_matfree_tensor(poms_ctx* ctx, int ndim, const poms_layout* layout, const int* nel, const int* nq,
+                                  const int* p, const int* const* first, const int* const* es, const int* const* ee,
+                                  const double* const* basis, const double* const* weights, const int64_t* nglob,
+                                  const double* g_q, int ncomp, const double* c_q, double mass_coef, poms_op** op);
 /* diag(A) of the interior rows, dense C order, HOST output: the stored diagonal of a
  * matrix-free operator, the centre coefficients of a general-stencil operator.   */
 int poms_op_diagonal(poms_op* op, double* diag_host);

@@ -24,6 +24,7 @@ __all__ = [
     "SplinePoints", "Binning", "evaluate_at", "deposit",
     "galerkin_stencil", "GalerkinVCycle",
     "MatrixFreeOperator", "MatrixFreeVCycle",
+    "Mapping", "SplineMapping", "MappedDomain", "pullback",
 ]
 
 
@@ -62,6 +63,9 @@ def __getattr__(name):
     if name in ("MatrixFreeOperator", "MatrixFreeVCycle"):
         from . import matfree
         return getattr(matfree, name)
+    if name in ("Mapping", "SplineMapping", "MappedDomain", "pullback"):
+        from . import geometry
+        return getattr(geometry, name)
     if name == "SlabDistribution":
         from .dist import SlabDistribution
         return SlabDistribution

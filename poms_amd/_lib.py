@@ -70,6 +70,10 @@ _SIGS = {
     "poms_op_assemble_stencil": [_vp, _i, _LP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _i64,
                                  _pp],
     "poms_op_create_matfree": [_vp, _i, _LP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _pp],
+    "poms_op_assemble_stencil_tensor": [_vp, _i, _LP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _d,
+                                        _i64, _pp],
+    "poms_op_create_matfree_tensor": [_vp, _i, _LP, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _d,
+                                      _pp],
     "poms_op_diagonal": [_vp, _vp],
     "poms_op_stencil_data": [_vp, _vp],
     "poms_op_galerkin_stencil": [_vp, _LP, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_void_p), _pp],

@@ -14,6 +14,17 @@ With ``a = c = 1`` this is ``assembly_2d``'s operator (pinned by its golden
 stencils); variable ``a``/``c`` (callables on the quadrature grid, or arrays of
 its shape) give operators that are not Kronecker sums, applied by the
 general-stencil kernel.
+
+``a`` may also be a full symmetric *tensor* ``G`` at the quadrature points
+(``poms_op_assemble_stencil_tensor``), the operator of a mapped domain or of
+anisotropic diffusion,
+
+    M[i, j] = Σ_e Σ_q w_q (c φ_i φ_j + ∇φ_iᵀ G ∇φ_j)
+
+given as ``d(d+1)/2`` component planes, the upper triangle in row-major order
+(3D: 00 01 02 11 12 22; 2D: 00 01 11): an array or a float64 device tensor of shape
+``(ncomp,) + quad_shape``.  One more dimension than the quadrature grid is what
+tells it from a scalar field.
 """
 from __future__ import annotations
 
@@ -123,12 +134,70 @@ def _coef_field(f, tabs, device):
     return torch.from_numpy(np.array(vals, dtype=np.float64, order="C")).to(device)
 
 
+def _device_field(f, tabs, device):
+    """A scalar field that is already a device tensor, used in place after the checks of
+    :func:`tensor_coef`."""
+    shape = tuple(t["nel"] * t["nq"] for t in tabs)
+    if f.dtype != torch.float64:
+        raise TypeError(f"coefficient tensor must be float64, got {f.dtype}")
+    if tuple(f.shape) != shape:
+        raise ValueError(f"coefficient tensor has shape {tuple(f.shape)}, the quadrature grid {shape}")
+    if f.device != torch.device(device):
+        raise ValueError(f"coefficient tensor lives on {f.device}, the space on {device}")
+    if not f.is_contiguous():
+        raise ValueError("coefficient tensor must be contiguous (C order)")
+    return f
+
+
+def tensor_ncomp(ndim: int) -> int:
+    """Components of a symmetric ``ndim`` x ``ndim`` tensor coefficient."""
+    return ndim * (ndim + 1) // 2
+
+
+def split_coef(f, tabs):
+    """``(values, is_tensor)``: a callable is sampled once at the quadrature points
+    (``meshgrid``, ``indexing='ij'``); what has one dimension more than the quadrature
+    grid is a tensor coefficient, anything else a scalar field."""
+    if f is None:
+        return None, False
+    if callable(f):
+        f = f(*np.meshgrid(*[t["points"].reshape(-1) for t in tabs], indexing="ij"))
+    ndim = f.dim() if isinstance(f, torch.Tensor) else np.ndim(f)
+    return f, ndim == len(tabs) + 1
+
+
+def tensor_coef(g, tabs, device):
+    """A tensor coefficient as the contiguous float64 device array of shape
+    ``(ncomp,) + quad_shape`` the operators read: a float64 device tensor of that shape
+    is used in place, an array is uploaded."""
+    qshape = tuple(t["nel"] * t["nq"] for t in tabs)
+    ncomp = tensor_ncomp(len(tabs))
+    want = (ncomp,) + qshape
+    got = tuple(g.shape) if isinstance(g, torch.Tensor) else np.shape(g)
+    if len(got) != len(want) or got[1:] != qshape:
+        raise ValueError(f"tensor coefficient has shape {got}, the quadrature grid needs {want}")
+    if got[0] != ncomp:
+        raise ValueError(f"tensor coefficient has {got[0]} components (shape {got}), a {len(tabs)}D operator "
+                         f"needs ncomp = {ncomp}: the upper triangle in row-major order")
+    if isinstance(g, torch.Tensor):
+        if g.dtype != torch.float64:
+            raise TypeError(f"tensor coefficient must be float64, got {g.dtype}")
+        if g.device != torch.device(device):
+            raise ValueError(f"tensor coefficient lives on {g.device}, the space on {device}")
+        if not g.is_contiguous():
+            raise ValueError("tensor coefficient must be contiguous (C order)")
+        return g
+    return torch.from_numpy(np.array(g, dtype=np.float64, order="C")).to(device)
+
+
 def assemble_stencil(V: StencilVectorSpace, knots, a=None, c=None, mass_coef: float = 1.0,
                      nquad: int | None = None) -> StencilMatrix:
     """``-∇·(a ∇u) + c u`` on the tensor space of ``knots`` (one knot vector per axis,
     degree = the space's pads), assembled on the device.  ``a``/``c``: None (1 and
     ``mass_coef``), a callable of the quadrature-point coordinates (``meshgrid``,
-    ``indexing='ij'``) or an array of the quadrature grid's shape."""
+    ``indexing='ij'``) or an array of the quadrature grid's shape.  ``a`` may be a
+    tensor coefficient: an array, a float64 device tensor, or a callable returning
+    either, of shape ``(ncomp,) + quad_shape`` (see the module's text)."""
     nd = V.ndim
     if len(knots) != nd:
         raise ValueError(f"{nd}D space needs {nd} knot vectors")
@@ -153,11 +222,18 @@ def assemble_stencil(V: StencilVectorSpace, knots, a=None, c=None, mass_coef: fl
     pp = (C.c_int * 3)(*ints("p"))
     nglob = (C.c_int64 * 3)(*([1] * lead + [int(t["n"]) for t in tabs]))
     dev = f"cuda:{V.device}"
-    aq, cq = _coef_field(a, tabs, dev), _coef_field(c, tabs, dev)
+    avals, tensor = split_coef(a, tabs)
+    aq = tensor_coef(avals, tabs, dev) if tensor else _coef_field(avals, tabs, dev)
+    cq = _device_field(c, tabs, dev) if isinstance(c, torch.Tensor) and c.is_cuda else _coef_field(c, tabs, dev)
     h = C.c_void_p()
-    _lib.call("poms_op_assemble_stencil", V.ctx, nd, C.byref(V.layout), nel, nq, pp,
-              arr3("first", C.c_int, np.int32), arr3("es", C.c_int, np.int32), arr3("ee", C.c_int, np.int32),
-              arr3("basis", C.c_double, np.float64), arr3("weights", C.c_double, np.float64), nglob,
-              None if aq is None else C.c_void_p(aq.data_ptr()), None if cq is None else C.c_void_p(cq.data_ptr()),
-              float(mass_coef), int(V.starts[0]) if nd == 3 else 0, C.byref(h))
+    tables = (arr3("first", C.c_int, np.int32), arr3("es", C.c_int, np.int32), arr3("ee", C.c_int, np.int32),
+              arr3("basis", C.c_double, np.float64), arr3("weights", C.c_double, np.float64), nglob)
+    tail = (None if cq is None else C.c_void_p(cq.data_ptr()), float(mass_coef),
+            int(V.starts[0]) if nd == 3 else 0, C.byref(h))
+    if tensor:
+        _lib.call("poms_op_assemble_stencil_tensor", V.ctx, nd, C.byref(V.layout), nel, nq, pp, *tables,
+                  C.c_void_p(aq.data_ptr()), tensor_ncomp(nd), *tail)
+    else:
+        _lib.call("poms_op_assemble_stencil", V.ctx, nd, C.byref(V.layout), nel, nq, pp, *tables,
+                  None if aq is None else C.c_void_p(aq.data_ptr()), *tail)
     return StencilMatrix._from_handle(V, h)

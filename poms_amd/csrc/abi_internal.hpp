@@ -41,11 +41,13 @@ struct poms_op {
     int sp[3]{};              // FORM_STENCIL: stencil half-widths per axis
     // FORM_MATFREE (poms_op_create_matfree): the per-axis device tables (owned, mf_tabs),
     // the stored diagonal (dense C order, owned), the borrowed coefficient arrays at the
-    // quadrature points (null: a = 1, c = mf_mass) and the launch geometry
+    // quadrature points (null: a = 1, c = mf_mass; mf_tensor: mf_a is the array of
+    // component planes of a tensor coefficient) and the launch geometry
     poms::AssembleAxis mf_ax[3]{};
     std::vector<void*> mf_tabs;
     double* mf_diag = nullptr;
     const double *mf_a = nullptr, *mf_c = nullptr;
+    bool mf_tensor = false;
     double mf_mass = 1.0;
     poms::MatfreeGeom mf_geom{};
     uint64_t gen = 0;   // bumped by every setter that changes the launches a graph would capture

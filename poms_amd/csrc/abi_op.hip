@@ -258,31 +258,35 @@ int poms_op_create_stencil(poms_ctx* ctx, int ndim, const poms_layout* layout, c
     return 0;
 }
 
-// On-device assembly of -div(a grad u) + c u into a FORM_STENCIL operator.
-int poms_op_assemble_stencil(poms_ctx* ctx, int ndim, const poms_layout* layout, const int* nel, const int* nq,
-                             const int* p, const int* const* first, const int* const* es, const int* const* ee,
-                             const double* const* basis, const double* const* weights, const int64_t* nglob,
-                             const double* a_q, const double* c_q, double mass_coef, int64_t g0, poms_op** op) {
+}  // extern "C"
+
+// On-device assembly of -div(a grad u) + c u into a FORM_STENCIL operator; tensor: a_q
+// holds the ndim (ndim + 1) / 2 component planes of a tensor coefficient.
+static int assemble_stencil_impl(const std::string& fn, poms_ctx* ctx, int ndim, const poms_layout* layout,
+                                 const int* nel, const int* nq, const int* p, const int* const* first,
+                                 const int* const* es, const int* const* ee, const double* const* basis,
+                                 const double* const* weights, const int64_t* nglob, const double* a_q, bool tensor,
+                                 const double* c_q, double mass_coef, int64_t g0, poms_op** op) {
     if (!ctx || !op || !layout_ok(layout) || !nel || !nq || !p || !first || !es || !ee || !basis || !weights || !nglob) {
-        set_error("poms_op_assemble_stencil: bad argument");
+        set_error(fn + ": bad argument");
         return 1;
     }
-    if (ndim < 1 || ndim > 3) { set_error("poms_op_assemble_stencil: ndim 1..3"); return 1; }
+    if (ndim < 1 || ndim > 3) { set_error(fn + ": ndim 1..3"); return 1; }
     const int d0 = 3 - ndim;
     for (int d = 0; d < d0; ++d)
         if (layout->n[d] != 1 || layout->pads[d] != 0) {
-            set_error("poms_op_assemble_stencil: unused leading axes need n = 1, pads = 0");
+            set_error(fn + ": unused leading axes need n = 1, pads = 0");
             return 1;
         }
     for (int d = d0; d < 3; ++d) {
         if (p[d] != layout->pads[d] || nel[d] < 1 || nq[d] < 1 || !first[d] || !es[d] || !ee[d] || !basis[d] ||
             !weights[d]) {
-            set_error("poms_op_assemble_stencil: axis " + std::to_string(d) + " (degree must equal the pad)");
+            set_error(fn + ": axis " + std::to_string(d) + " (degree must equal the pad)");
             return 1;
         }
-        if (d > 0 && nglob[d] != layout->n[d]) { set_error("poms_op_assemble_stencil: only axis 0 may be sliced"); return 1; }
+        if (d > 0 && nglob[d] != layout->n[d]) { set_error(fn + ": only axis 0 may be sliced"); return 1; }
     }
-    if (ndim == 3 && (g0 < 0 || g0 + layout->n[0] > nglob[0])) { set_error("poms_op_assemble_stencil: bad slab"); return 1; }
+    if (ndim == 3 && (g0 < 0 || g0 + layout->n[0] > nglob[0])) { set_error(fn + ": bad slab"); return 1; }
     POMS_HIP_CHECK(hipSetDevice(ctx->device));
     const RowGeom r = row_geom(layout);
     const int64_t W = (int64_t)(2 * r.pd0 + 1) * (2 * r.pd1 + 1) * (2 * r.pd2 + 1);
@@ -330,12 +334,12 @@ int poms_op_assemble_stencil(poms_ctx* ctx, int ndim, const poms_layout* layout,
     if (!rc && hipMalloc(reinterpret_cast<void**>(&o->coef), std::max<int64_t>(W * cst, 1) * sizeof(double)) != hipSuccess)
         rc = 1;
     if (!rc) {
-        assemble_launch(ax, (int)o->g0, r.n0, a_q, c_q, mass_coef, o->coef, nullptr);
+        assemble_launch(ax, (int)o->g0, r.n0, a_q, c_q, mass_coef, o->coef, nullptr, tensor ? ndim : 0);
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = 1;
     }
     for (void* d : tmp) (void)hipFree(d);
     if (rc) {
-        set_error("poms_op_assemble_stencil: allocation, upload or launch failed");
+        set_error(fn + ": allocation, upload or launch failed");
         poms_op_destroy(o);
         return 1;
     }
@@ -344,17 +348,25 @@ int poms_op_assemble_stencil(poms_ctx* ctx, int ndim, const poms_layout* layout,
 }
 
 // The matrix-free form of -div(a grad u) + c u (csrc/matfree.hip).  The kernel indexes
-// with the tables unguarded: every check comes first, before any device call.
-int poms_op_create_matfree(poms_ctx* ctx, int ndim, const poms_layout* layout, const int* nel, const int* nq,
-                           const int* p, const int* const* first, const int* const* es, const int* const* ee,
-                           const double* const* basis, const double* const* weights, const int64_t* nglob,
-                           const double* a_q, const double* c_q, double mass_coef, poms_op** op) {
-    const std::string fn = "poms_op_create_matfree: ";
-    if (!ctx || !op || !layout || !nel || !nq || !p || !first || !es || !ee || !basis || !weights || !nglob) {
+// with the tables unguarded: every check comes first, before any device call.  tensor:
+// a_q holds the ncomp component planes of a tensor coefficient (not null).
+static int create_matfree_impl(const std::string& name, poms_ctx* ctx, int ndim, const poms_layout* layout,
+                               const int* nel, const int* nq, const int* p, const int* const* first,
+                               const int* const* es, const int* const* ee, const double* const* basis,
+                               const double* const* weights, const int64_t* nglob, const double* a_q, bool tensor,
+                               int ncomp, const double* c_q, double mass_coef, poms_op** op) {
+    const std::string fn = name + ": ";
+    if (!ctx || !op || !layout || !nel || !nq || !p || !first || !es || !ee || !basis || !weights || !nglob ||
+        (tensor && !a_q)) {
         set_error(fn + "null argument");
         return 1;
     }
     if (ndim != 2 && ndim != 3) { set_error(fn + "ndim must be 2 or 3"); return 1; }
+    if (tensor && ncomp != ndim * (ndim + 1) / 2) {
+        set_error(fn + "ncomp must be d (d + 1) / 2 = " + std::to_string(ndim * (ndim + 1) / 2) + ", got " +
+                  std::to_string(ncomp));
+        return 1;
+    }
     if (!layout_ok(layout)) { set_error(fn + "bad layout"); return 1; }
     if (layout->flags & POMS_LAYOUT_GHOST_DATA) {
         set_error(fn + "distributed operators (slabs, Cart blocks) are not supported");
@@ -402,6 +414,10 @@ int poms_op_create_matfree(poms_ctx* ctx, int ndim, const poms_layout* layout, c
     const int64_t ndof = layout->n[0] * layout->n[1] * layout->n[2];
     if (ndof > ((int64_t)1 << 36)) { set_error(fn + "grid too large"); return 1; }
     POMS_HIP_CHECK(hipSetDevice(ctx->device));
+    if (tensor) {
+        std::string why;
+        if (!matfree_tensor_builds_ok(&why)) { set_error(fn + why); return 1; }
+    }
     const RowGeom r = row_geom(layout);
     auto* o = new poms_op();
     o->ctx = ctx;
@@ -413,6 +429,7 @@ int poms_op_create_matfree(poms_ctx* ctx, int ndim, const poms_layout* layout, c
     o->n0g = ndim == 3 ? nglob[0] : 1;
     o->sp[0] = r.pd0; o->sp[1] = r.pd1; o->sp[2] = r.pd2;
     o->mf_a = a_q;
+    o->mf_tensor = tensor;
     o->mf_c = c_q;
     o->mf_mass = mass_coef;
     auto up = [&](const void* h, size_t bytes) -> void* {
@@ -441,7 +458,7 @@ int poms_op_create_matfree(poms_ctx* ctx, int ndim, const poms_layout* layout, c
     if (!rc && hipMalloc(reinterpret_cast<void**>(&o->mf_diag), std::max<int64_t>(ndof, 1) * sizeof(double)) != hipSuccess)
         rc = 1;
     if (!rc) {
-        matfree_diag_launch(o->mf_ax, a_q, c_q, mass_coef, o->mf_diag, nullptr);
+        matfree_diag_launch(o->mf_ax, a_q, c_q, mass_coef, o->mf_diag, nullptr, tensor ? ndim : 0);
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = 1;
     }
     if (rc) {
@@ -470,6 +487,52 @@ int poms_op_create_matfree(poms_ctx* ctx, int ndim, const poms_layout* layout, c
     g.ntiles = t12 * g.nchunks;
     *op = o;
     return 0;
+}
+
+extern "C" {
+
+int poms_op_assemble_stencil(poms_ctx* ctx, int ndim, const poms_layout* layout, const int* nel, const int* nq,
+                             const int* p, const int* const* first, const int* const* es, const int* const* ee,
+                             const double* const* basis, const double* const* weights, const int64_t* nglob,
+                             const double* a_q, const double* c_q, double mass_coef, int64_t g0, poms_op** op) {
+    return assemble_stencil_impl("poms_op_assemble_stencil", ctx, ndim, layout, nel, nq, p, first, es, ee, basis,
+                                 weights, nglob, a_q, false, c_q, mass_coef, g0, op);
+}
+
+int poms_op_assemble_stencil_tensor(poms_ctx* ctx, int ndim, const poms_layout* layout, const int* nel, const int* nq,
+                                    const int* p, const int* const* first, const int* const* es,
+                                    const int* const* ee, const double* const* basis, const double* const* weights,
+                                    const int64_t* nglob, const double* g_q, int ncomp, const double* c_q,
+                                    double mass_coef, int64_t g0, poms_op** op) {
+    const std::string fn = "poms_op_assemble_stencil_tensor";
+    if (!ctx || !op || !layout || !nel || !nq || !p || !first || !es || !ee || !basis || !weights || !nglob || !g_q) {
+        set_error(fn + ": null argument");
+        return 1;
+    }
+    if (ndim < 1 || ndim > 3) { set_error(fn + ": ndim 1..3"); return 1; }
+    if (ncomp != ndim * (ndim + 1) / 2) {
+        set_error(fn + ": ncomp must be d (d + 1) / 2 = " + std::to_string(ndim * (ndim + 1) / 2) + ", got " +
+                  std::to_string(ncomp));
+        return 1;
+    }
+    return assemble_stencil_impl(fn, ctx, ndim, layout, nel, nq, p, first, es, ee, basis, weights, nglob, g_q, true,
+                                 c_q, mass_coef, g0, op);
+}
+
+int poms_op_create_matfree(poms_ctx* ctx, int ndim, const poms_layout* layout, const int* nel, const int* nq,
+                           const int* p, const int* const* first, const int* const* es, const int* const* ee,
+                           const double* const* basis, const double* const* weights, const int64_t* nglob,
+                           const double* a_q, const double* c_q, double mass_coef, poms_op** op) {
+    return create_matfree_impl("poms_op_create_matfree", ctx, ndim, layout, nel, nq, p, first, es, ee, basis, weights,
+                               nglob, a_q, false, 0, c_q, mass_coef, op);
+}
+
+int poms_op_create_matfree_tensor(poms_ctx* ctx, int ndim, const poms_layout* layout, const int* nel, const int* nq,
+                                  const int* p, const int* const* first, const int* const* es, const int* const* ee,
+                                  const double* const* basis, const double* const* weights, const int64_t* nglob,
+                                  const double* g_q, int ncomp, const double* c_q, double mass_coef, poms_op** op) {
+    return create_matfree_impl("poms_op_create_matfree_tensor", ctx, ndim, layout, nel, nq, p, first, es, ee, basis,
+                               weights, nglob, g_q, true, ncomp, c_q, mass_coef, op);
 }
 
 int poms_op_diagonal(poms_op* o, double* diag_host) {
@@ -927,7 +990,8 @@ static int matfree_run(poms_op* o, int epi, double omega, const double* x, doubl
     const int nblk = (int)std::min<int64_t>(g.ntiles, maxb);
     const bool wd = want_dot || epi == EPI_APPLYDOT;
     if (matfree_launch(epi, g, o->mf_ax, x, y, b, o->mf_a, o->mf_c, o->mf_diag, o->mf_mass, omega,
-                       want_norm ? scr : nullptr, wd ? scr + nblk : nullptr, maxb, as_stream(stream), &nb))
+                       want_norm ? scr : nullptr, wd ? scr + nblk : nullptr, maxb, as_stream(stream), &nb,
+                       o->mf_tensor))
         return 1;
     POMS_HIP_CHECK(hipGetLastError());
     o->last_partials = (want_norm || wd) ? nb : 0;

@@ -70,6 +70,42 @@ struct AssembleAxis {
     int nel, nq, p, n;
 };
 
+// A symmetric tensor coefficient at one quadrature point (the kernels' 3-axis numbering).
+// The device array holds ncomp = d(d+1)/2 component planes of `gs` points each, the
+// upper triangle in row-major order of the operator's axes: 3D 00 01 02 11 12 22,
+// 2D 11 12 22, 1D 22; the entries of an unused leading axis are not read and stay 0.
+struct Tensor6 {
+    double g00 = 0.0, g01 = 0.0, g02 = 0.0, g11 = 0.0, g12 = 0.0, g22 = 0.0;
+};
+
+__device__ __forceinline__ void tensor_load(Tensor6& t, const double* __restrict__ g_q, int64_t qi, int64_t gs,
+                                            int ndim) {
+    if (ndim == 3) {
+        t.g00 = g_q[qi];
+        t.g01 = g_q[gs + qi];
+        t.g02 = g_q[2 * gs + qi];
+        t.g11 = g_q[3 * gs + qi];
+        t.g12 = g_q[4 * gs + qi];
+        t.g22 = g_q[5 * gs + qi];
+    } else if (ndim == 2) {
+        t.g11 = g_q[qi];
+        t.g12 = g_q[gs + qi];
+        t.g22 = g_q[2 * gs + qi];
+    } else {
+        t.g22 = g_q[qi];
+    }
+}
+
+// u^T G v with all nine products: row i of G v first (g_i0 v0 + g_i1 v1 + g_i2 v2, in
+// that order with fmas), then the sum over the rows (assembly and the stored diagonal)
+__device__ __forceinline__ double tensor_form(const Tensor6& t, double u0, double u1, double u2, double v0, double v1,
+                                              double v2) {
+    const double r0 = fma(t.g02, v2, fma(t.g01, v1, t.g00 * v0));
+    const double r1 = fma(t.g12, v2, fma(t.g11, v1, t.g01 * v0));
+    const double r2 = fma(t.g22, v2, fma(t.g12, v1, t.g02 * v0));
+    return fma(u2, r2, fma(u1, r1, u0 * r0));
+}
+
 // One launch of the matrix-free operator (matfree.hip): tiles of matfree_tile() output
 // columns on axes 1 and 2, chunks of `chunk` output planes on axis 0.
 struct MatfreeGeom {

@@ -53,8 +53,10 @@ int diag_scale_launch(bool is3d, int form, const RowGeom& g, int P, int g0, doub
 int dense_matvec_launch(int n, const double* M, const double* x, double* y, hipStream_t st);
 
 // ---- stencil_general.hip ----------------------------------------------------------
+// (tensor_ndim = 2 or 3: a_q holds the component planes of a tensor coefficient, see
+// common.hpp's Tensor6; 0: a scalar field or null)
 int assemble_launch(const AssembleAxis* ax, int g0, int nl0, const double* a_q, const double* c_q, double mass_coef,
-                    double* coef, hipStream_t st);
+                    double* coef, hipStream_t st, int tensor_ndim = 0);
 int stencil_to_spl_launch(const StencilGeom& g, const double* coef, double* out, hipStream_t st);
 int stencil_launch(int epi, const StencilGeom& g, const double* coef, const double* x, double* y,
                    const double* b, double omega, double* partial, double* partial2, int max_blocks,
@@ -64,11 +66,14 @@ int stencil_launch(int epi, const StencilGeom& g, const double* coef, const doub
 int matfree_tile();           // output columns per tile edge (axes 1, 2)
 int matfree_max_window();     // widest x window a tile may need per axis
 int matfree_max_elements();   // most elements a tile may touch per axis
+// (tensor / tensor_ndim as assemble_launch's: a_q is then the tensor's component planes)
 int matfree_diag_launch(const AssembleAxis* ax, const double* a_q, const double* c_q, double mass_coef, double* diag,
-                        hipStream_t st);
+                        hipStream_t st, int tensor_ndim = 0);
 int matfree_launch(int epi, const MatfreeGeom& g, const AssembleAxis* ax, const double* x, double* y, const double* b,
                    const double* a_q, const double* c_q, const double* diag, double mass_coef, double omega,
-                   double* partial, double* partial2, int max_blocks, hipStream_t st, int* nblk_out);
+                   double* partial, double* partial2, int max_blocks, hipStream_t st, int* nblk_out,
+                   bool tensor = false);
+bool matfree_tensor_builds_ok(std::string* why);   // no scratch, at most 256 registers
 
 // ---- stencil_galerkin.hip ---------------------------------------------------------
 // One axis of the Galerkin product P^T A P of a general stencil: coefficient planes

@@ -30,6 +30,13 @@
 // give the same bits.  Only interior entries of y are stored; x is read inside its
 // window, which lies in the interior of its storage.
 //
+// TENSOR builds apply -div(G grad u) + c u with a full symmetric tensor G at the points
+// (a mapped domain, G = a |det J| J^-1 J^-T, or anisotropic diffusion): a_q is then the
+// array of component planes (common.hpp, Tensor6), and only stage C and its prefetch
+// differ -- a wave fetches the tensor's entries and c_q of its next row a round ahead and
+// writes the three fluxes f_i = w (g_i0 d0u + g_i1 d1u + g_i2 d2u) where w a d_iu goes
+// otherwise.  A 2D operator's entries on axis 0 are not read and count as 0.
+//
 // The host (poms_op_create_matfree) checks every table entry the kernel indexes with
 // and that every tile's window fits the LDS arrays below.
 #include "common.hpp"
@@ -51,7 +58,7 @@ int matfree_tile() { return MF_D; }
 int matfree_max_window() { return MF_W; }
 int matfree_max_elements() { return MF_E; }
 
-template <int EPI>
+template <int EPI, bool TENSOR>
 __global__ void __launch_bounds__(256)
 matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1, const AssembleAxis A2,
                const double* __restrict__ x, double* __restrict__ y, const double* __restrict__ b,
@@ -79,6 +86,10 @@ matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1
     const int i1l = tid / MF_D, i2l = tid % MF_D;   // this thread's output column (tid < 64)
     const int wr = tid >> 4, wc = tid & 15;          // this thread's window entry (MF_W <= 16)
     const int darr = lane / MF_D, dil = lane % MF_D; // stage D: array and column of lanes 0..23
+    // TENSOR: points per component plane, and the operator's dimension (a 2D operator
+    // has the trivial axis 0, p = 0)
+    const int64_t gs = TENSOR ? (int64_t)A0.nel * nq0 * NQ1 * NQ2 : 0;
+    const int gdim = p0 > 0 ? 3 : 2;
     double nrm = 0.0, dot = 0.0;
     for (int64_t t = blockIdx.x; t < g.ntiles; t += gridDim.x) {
         const int t2 = (int)(t % g.tiles2), t1 = (int)((t / g.tiles2) % g.tiles1);
@@ -148,9 +159,14 @@ matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1
                 const int64_t qrow = (int64_t)q0g * NQ1 + (int64_t)E1lo * nq1;
                 // the coefficients of this wave's first row (each round fetches the next round's)
                 double an = 1.0, cn = mass_coef;
+                Tensor6 gn;
                 if (wave < Q1 && lane < Q2) {
                     const int64_t qi = (qrow + wave) * NQ2 + (E2lo * nq2 + lane);
-                    if (a_q) an = a_q[qi];
+                    if constexpr (TENSOR) {
+                        tensor_load(gn, a_q, qi, gs, gdim);
+                    } else {
+                        if (a_q) an = a_q[qi];
+                    }
                     if (c_q) cn = c_q[qi];
                 }
                 // A: contract the p0+1 window planes with B0, B0'
@@ -188,9 +204,14 @@ matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1
                 for (int r = 0; r < rounds; ++r) {
                     const int q1 = r * 4 + wave;
                     const double ca = an, cc = cn;
+                    const Tensor6 cg = gn;
                     if (q1 + 4 < Q1 && lane < Q2) {
                         const int64_t qi = (qrow + q1 + 4) * NQ2 + (E2lo * nq2 + lane);
-                        if (a_q) an = a_q[qi];
+                        if constexpr (TENSOR) {
+                            tensor_load(gn, a_q, qi, gs, gdim);
+                        } else {
+                            if (a_q) an = a_q[qi];
+                        }
                         if (c_q) cn = c_q[qi];
                     }
                     if (q1 < Q1 && lane < Q2) {
@@ -208,9 +229,15 @@ matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1
                         const double wa = w * ca;
                         const double wc_ = w * cc;
                         G[lane] = wc_ * u;
-                        G[MF_Q + lane] = wa * d0;
-                        G[2 * MF_Q + lane] = wa * d1;
-                        G[3 * MF_Q + lane] = wa * d2;
+                        if constexpr (TENSOR) {
+                            G[MF_Q + lane] = w * fma(cg.g02, d2, fma(cg.g01, d1, cg.g00 * d0));
+                            G[2 * MF_Q + lane] = w * fma(cg.g12, d2, fma(cg.g11, d1, cg.g01 * d0));
+                            G[3 * MF_Q + lane] = w * fma(cg.g22, d2, fma(cg.g12, d1, cg.g02 * d0));
+                        } else {
+                            G[MF_Q + lane] = wa * d0;
+                            G[2 * MF_Q + lane] = wa * d1;
+                            G[3 * MF_Q + lane] = wa * d2;
+                        }
                     }
                     __syncthreads();
                     // (G is the wave's own: its next round's stores follow these loads in
@@ -292,16 +319,19 @@ matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1
 
 // diag[i] = sum_q w (c phi_i^2 + a |grad phi_i|^2): assemble_kernel's centre offset
 // (stencil_general.hip; the same expression, per element the quadrature sum first),
-// one thread per row, dense C order.
+// one thread per row, dense C order.  TENSOR: sum_q w (c phi_i^2 + grad phi_i^T G grad
+// phi_i), a_q the component planes of an ndim-dimensional operator.
+template <bool TENSOR>
 __global__ void __launch_bounds__(256)
 matfree_diag_kernel(const AssembleAxis A0, const AssembleAxis A1, const AssembleAxis A2,
                     const double* __restrict__ a_q, const double* __restrict__ c_q, double mass_coef,
-                    double* __restrict__ diag) {
+                    double* __restrict__ diag, int ndim) {
     const int64_t total = (int64_t)A0.n * A1.n * A2.n;
     const int64_t lin = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (lin >= total) return;
     const int i2 = (int)(lin % A2.n), i1 = (int)((lin / A2.n) % A1.n), i0 = (int)(lin / ((int64_t)A2.n * A1.n));
     const int64_t NQ1 = (int64_t)A1.nel * A1.nq, NQ2 = (int64_t)A2.nel * A2.nq;
+    const int64_t gs = (int64_t)A0.nel * A0.nq * NQ1 * NQ2;
     double tot = 0.0;
     for (int e0 = A0.es[i0]; e0 <= A0.ee[i0]; ++e0) {
         const int l0 = i0 - A0.first[e0];
@@ -325,9 +355,17 @@ matfree_diag_kernel(const AssembleAxis A0, const AssembleAxis A1, const Assemble
                             const double gz = (b0 * (b1 * d2)) * (b0 * (b1 * d2));
                             const int64_t qi = ((int64_t)(e0 * A0.nq + q0) * NQ1 + (e1 * A1.nq + q1)) * NQ2 +
                                                (e2 * A2.nq + q2);
-                            const double ca = a_q ? a_q[qi] : 1.0;
                             const double cc = c_q ? c_q[qi] : mass_coef;
-                            v = fma(cc * i_0 * i_0 + ca * (gx + gy + gz), w0 * (w1 * w2), v);
+                            if constexpr (TENSOR) {
+                                Tensor6 t;
+                                tensor_load(t, a_q, qi, gs, ndim);
+                                const double e_0 = d0 * (b1 * b2), e_1 = b0 * (d1 * b2), e_2 = b0 * (b1 * d2);
+                                const double form = tensor_form(t, e_0, e_1, e_2, e_0, e_1, e_2);
+                                v = fma(cc * i_0 * i_0 + form, w0 * (w1 * w2), v);
+                            } else {
+                                const double ca = a_q ? a_q[qi] : 1.0;
+                                v = fma(cc * i_0 * i_0 + ca * (gx + gy + gz), w0 * (w1 * w2), v);
+                            }
                         }
                     }
                 }
@@ -339,25 +377,59 @@ matfree_diag_kernel(const AssembleAxis A0, const AssembleAxis A1, const Assemble
 }
 
 int matfree_diag_launch(const AssembleAxis* ax, const double* a_q, const double* c_q, double mass_coef, double* diag,
-                        hipStream_t st) {
+                        hipStream_t st, int tensor_ndim) {
     const int64_t total = (int64_t)ax[0].n * ax[1].n * ax[2].n;
     if (total == 0) return 0;
-    hipLaunchKernelGGL(matfree_diag_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ax[0], ax[1],
-                       ax[2], a_q, c_q, mass_coef, diag);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (tensor_ndim)
+        hipLaunchKernelGGL(matfree_diag_kernel<true>, grid, dim3(256), 0, st, ax[0], ax[1], ax[2], a_q, c_q, mass_coef,
+                           diag, tensor_ndim);
+    else
+        hipLaunchKernelGGL(matfree_diag_kernel<false>, grid, dim3(256), 0, st, ax[0], ax[1], ax[2], a_q, c_q,
+                           mass_coef, diag, 0);
     return 0;
+}
+
+// The tensor builds run two workgroups per CU like the scalar ones (the LDS sets that):
+// any number of registers up to 256 keeps that, scratch does not.  False, with a
+// message, if a build reports scratch or the attributes cannot be read.
+bool matfree_tensor_builds_ok(std::string* why) {
+    const void* fns[4] = {(const void*)matfree_kernel<EPI_APPLY, true>, (const void*)matfree_kernel<EPI_RESID, true>,
+                          (const void*)matfree_kernel<EPI_JACOBI, true>,
+                          (const void*)matfree_kernel<EPI_APPLYDOT, true>};
+    for (int k = 0; k < 4; ++k) {
+        hipFuncAttributes at{};
+        if (hipFuncGetAttributes(&at, fns[k]) != hipSuccess) {
+            (void)hipGetLastError();
+            *why = "the attributes of the tensor kernel could not be read";
+            return false;
+        }
+        if (at.localSizeBytes != 0 || at.numRegs > 256) {
+            *why = "tensor kernel build " + std::to_string(k) + " uses " + std::to_string(at.localSizeBytes) +
+                   " B of scratch and " + std::to_string(at.numRegs) + " registers (0 B and at most 256 allowed)";
+            return false;
+        }
+    }
+    return true;
 }
 
 // One workgroup per tile, at most max_blocks of them (the partials fit the scratch);
 // a workgroup then takes every gridDim-th tile.
 int matfree_launch(int epi, const MatfreeGeom& g, const AssembleAxis* ax, const double* x, double* y, const double* b,
                    const double* a_q, const double* c_q, const double* diag, double mass_coef, double omega,
-                   double* partial, double* partial2, int max_blocks, hipStream_t st, int* nblk_out) {
+                   double* partial, double* partial2, int max_blocks, hipStream_t st, int* nblk_out, bool tensor) {
     const int nb = (int)std::min<int64_t>(g.ntiles, max_blocks);
     *nblk_out = nb;
     if (nb <= 0) return 0;
-#define POMS_MF_LAUNCH(E)                                                                                       \
-    hipLaunchKernelGGL(matfree_kernel<E>, dim3(nb), dim3(256), 0, st, g, ax[0], ax[1], ax[2], x, y, b, a_q, c_q, \
-                       diag, mass_coef, omega, partial, partial2)
+#define POMS_MF_LAUNCH(E)                                                                                     \
+    do {                                                                                                      \
+        if (tensor)                                                                                           \
+            hipLaunchKernelGGL((matfree_kernel<E, true>), dim3(nb), dim3(256), 0, st, g, ax[0], ax[1], ax[2], x, y, \
+                               b, a_q, c_q, diag, mass_coef, omega, partial, partial2);                       \
+        else                                                                                                  \
+            hipLaunchKernelGGL((matfree_kernel<E, false>), dim3(nb), dim3(256), 0, st, g, ax[0], ax[1], ax[2], x, y, \
+                               b, a_q, c_q, diag, mass_coef, omega, partial, partial2);                       \
+    } while (0)
     switch (epi) {
         case EPI_APPLY: POMS_MF_LAUNCH(EPI_APPLY); break;
         case EPI_RESID: POMS_MF_LAUNCH(EPI_RESID); break;

@@ -90,11 +90,15 @@ stencil_kernel(const StencilGeom g, const double* __restrict__ coef, const doubl
 // share; per element the quadrature sum is formed first and then added, as the
 // reference's element loop does.  a_q / c_q: coefficients at every quadrature
 // point (index ((e0 nq0 + g0) NQ1 + e1 nq1 + g1) NQ2 + e2 nq2 + g2), or null for
-// a = 1, c = mass_coef.
+// a = 1, c = mass_coef.  TENSOR: -div(G grad u) + c u with a symmetric tensor at the
+// points, sum_q w (c phi_i phi_j + grad phi_i^T G grad phi_j) with all d^2 gradient
+// products; a_q is then the array of component planes of an ndim-dimensional operator
+// (common.hpp, Tensor6).
+template <bool TENSOR>
 __global__ void __launch_bounds__(256)
 assemble_kernel(const AssembleAxis A0, const AssembleAxis A1, const AssembleAxis A2, int g0, int nl0,
                 const double* __restrict__ a_q, const double* __restrict__ c_q, double mass_coef,
-                double* __restrict__ coef) {
+                double* __restrict__ coef, int ndim) {
     const int64_t cst = (int64_t)nl0 * A1.n * A2.n;
     const int W1 = 2 * A1.p + 1, W2 = 2 * A2.p + 1;
     const int64_t total = cst * (int64_t)(2 * A0.p + 1) * W1 * W2;
@@ -111,6 +115,7 @@ assemble_kernel(const AssembleAxis A0, const AssembleAxis A1, const AssembleAxis
         const int ea1 = max(A1.es[i1], A1.es[j1]), eb1 = min(A1.ee[i1], A1.ee[j1]);
         const int ea2 = max(A2.es[i2], A2.es[j2]), eb2 = min(A2.ee[i2], A2.ee[j2]);
         const int NQ1 = A1.nel * A1.nq, NQ2 = A2.nel * A2.nq;
+        const int64_t gs = (int64_t)A0.nel * A0.nq * NQ1 * NQ2;
         for (int e0 = ea0; e0 <= eb0; ++e0) {
             const int li0 = i0 - A0.first[e0], lj0 = j0 - A0.first[e0];
             for (int e1 = ea1; e1 <= eb1; ++e1) {
@@ -140,9 +145,18 @@ assemble_kernel(const AssembleAxis A0, const AssembleAxis A1, const AssembleAxis
                                 const double gz = (bi0 * (bi1 * di2)) * (bj0 * (bj1 * dj2));
                                 const int64_t qi = ((int64_t)(e0 * A0.nq + q0) * NQ1 + (e1 * A1.nq + q1)) * NQ2 +
                                                    (e2 * A2.nq + q2);
-                                const double ca = a_q ? a_q[qi] : 1.0;
                                 const double cc = c_q ? c_q[qi] : mass_coef;
-                                v = fma(cc * i_0 * j_0 + ca * (gx + gy + gz), w0 * (w1 * w2), v);
+                                if constexpr (TENSOR) {
+                                    Tensor6 t;
+                                    tensor_load(t, a_q, qi, gs, ndim);
+                                    const double form =
+                                        tensor_form(t, di0 * (bi1 * bi2), bi0 * (di1 * bi2), bi0 * (bi1 * di2),
+                                                    dj0 * (bj1 * bj2), bj0 * (dj1 * bj2), bj0 * (bj1 * dj2));
+                                    v = fma(cc * i_0 * j_0 + form, w0 * (w1 * w2), v);
+                                } else {
+                                    const double ca = a_q ? a_q[qi] : 1.0;
+                                    v = fma(cc * i_0 * j_0 + ca * (gx + gy + gz), w0 * (w1 * w2), v);
+                                }
                             }
                         }
                     }
@@ -155,11 +169,16 @@ assemble_kernel(const AssembleAxis A0, const AssembleAxis A1, const AssembleAxis
 }
 
 int assemble_launch(const AssembleAxis* ax, int g0, int nl0, const double* a_q, const double* c_q, double mass_coef,
-                    double* coef, hipStream_t st) {
+                    double* coef, hipStream_t st, int tensor_ndim) {
     const int64_t total = (int64_t)nl0 * ax[1].n * ax[2].n * (2 * ax[0].p + 1) * (2 * ax[1].p + 1) * (2 * ax[2].p + 1);
     if (total == 0) return 0;
-    hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ax[0], ax[1], ax[2],
-                       g0, nl0, a_q, c_q, mass_coef, coef);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (tensor_ndim)
+        hipLaunchKernelGGL(assemble_kernel<true>, grid, dim3(256), 0, st, ax[0], ax[1], ax[2], g0, nl0, a_q, c_q,
+                           mass_coef, coef, tensor_ndim);
+    else
+        hipLaunchKernelGGL(assemble_kernel<false>, grid, dim3(256), 0, st, ax[0], ax[1], ax[2], g0, nl0, a_q, c_q,
+                           mass_coef, coef, 0);
     return 0;
 }
 

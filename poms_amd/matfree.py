@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .assembly import _coef_field, assemble_stencil, axis_tables
+from .assembly import _coef_field, assemble_stencil, axis_tables, split_coef, tensor_coef, tensor_ncomp
 from .mg import GalerkinVCycle, two_level_setup_1d
 from .splines import uniform_knots
 from .stencil import KronOperator, StencilVectorSpace
@@ -51,6 +51,18 @@ def _coef_arg(f, tabs, device):
     return _coef_field(f, tabs, device)
 
 
+def _diffusion_arg(a, tabs, device):
+    """``(array, is_tensor)`` of the argument ``a``: a tensor coefficient (one dimension
+    more than the quadrature grid, :func:`~poms_amd.assembly.tensor_coef`) or what
+    :func:`_coef_arg` makes of a scalar field."""
+    vals, tensor = split_coef(a, tabs)
+    if tensor:
+        return tensor_coef(vals, tabs, device), True
+    if callable(a):
+        return _coef_field(vals, tabs, device), False
+    return _coef_arg(a, tabs, device), False
+
+
 class MatrixFreeOperator(KronOperator):
     """``-∇·(a∇u) + c u`` on the tensor space of ``knots`` (degree = the space's pads,
     1…3; ``nquad`` 1…5 Gauss points per element, default ``p+1``), applied matrix-free.
@@ -61,6 +73,13 @@ class MatrixFreeOperator(KronOperator):
     float64 device tensor of that shape, which is used in place without a copy: the
     operator keeps a reference, and later changes to the tensor change the operator
     (but not its diagonal, formed once at creation).
+
+    ``a`` may be a tensor coefficient ``G`` (``-∇·(G∇u) + c u``, a mapped domain or
+    anisotropic diffusion, ``poms_op_create_matfree_tensor``): an array, a float64
+    device tensor (used in place) or a callable returning either, of shape
+    ``(ncomp,) + quad_shape`` with the ``d(d+1)/2`` components of the upper triangle in
+    row-major order; one dimension more than the quadrature grid tells it from a
+    scalar field (:attr:`tensor` is then True).
 
     ``dot``, ``residual``, ``dot_inner``, ``jacobi_sweep`` and ``diag_scale`` run the
     kernel's epilogues; ``pcg``, ``damped_jacobi``, ``jacobi`` and ``crl`` take the
@@ -92,7 +111,7 @@ class MatrixFreeOperator(KronOperator):
         self.quad_shape = tuple(t["nel"] * t["nq"] for t in tabs)
         dev = f"cuda:{V.device}"
         # the arrays the handle borrows live as long as this object
-        self._aq, self._cq = _coef_arg(a, tabs, dev), _coef_arg(c, tabs, dev)
+        (self._aq, self.tensor), self._cq = _diffusion_arg(a, tabs, dev), _coef_arg(c, tabs, dev)
         self._diag = None
         lead = 3 - nd
         keep = []
@@ -108,13 +127,16 @@ class MatrixFreeOperator(KronOperator):
         ints = lambda key: [0] * lead + [int(t[key]) for t in tabs]
         nel, nq, pp = (C.c_int * 3)(*ints("nel")), (C.c_int * 3)(*ints("nq")), (C.c_int * 3)(*ints("p"))
         nglob = (C.c_int64 * 3)(*([1] * lead + [int(t["n"]) for t in tabs]))
+        tables = (arr3("first", np.int32), arr3("es", np.int32), arr3("ee", np.int32),
+                  arr3("basis", np.float64), arr3("weights", np.float64), nglob)
+        tail = (None if self._cq is None else C.c_void_p(self._cq.data_ptr()), self.mass_coef, C.byref(self._h))
         try:
-            _lib.call("poms_op_create_matfree", V.ctx, nd, C.byref(V.layout), nel, nq, pp,
-                      arr3("first", np.int32), arr3("es", np.int32), arr3("ee", np.int32),
-                      arr3("basis", np.float64), arr3("weights", np.float64), nglob,
-                      None if self._aq is None else C.c_void_p(self._aq.data_ptr()),
-                      None if self._cq is None else C.c_void_p(self._cq.data_ptr()),
-                      self.mass_coef, C.byref(self._h))
+            if self.tensor:
+                _lib.call("poms_op_create_matfree_tensor", V.ctx, nd, C.byref(V.layout), nel, nq, pp, *tables,
+                          C.c_void_p(self._aq.data_ptr()), tensor_ncomp(nd), *tail)
+            else:
+                _lib.call("poms_op_create_matfree", V.ctx, nd, C.byref(V.layout), nel, nq, pp, *tables,
+                          None if self._aq is None else C.c_void_p(self._aq.data_ptr()), *tail)
         except _lib.PomsError as e:
             raise ValueError(str(e)) from None
 
@@ -141,8 +163,9 @@ class MatrixFreeOperator(KronOperator):
         same arguments (for cross-checks and host-side views)."""
         a, c = self._args
         to_np = lambda f: f.cpu().numpy() if isinstance(f, torch.Tensor) else f
-        return assemble_stencil(self.space, self.knots, a=to_np(a), c=to_np(c), mass_coef=self.mass_coef,
-                                nquad=self.nquad)
+        # (a tensor coefficient goes on as the device array the operator holds)
+        return assemble_stencil(self.space, self.knots, a=self._aq if self.tensor else to_np(a), c=to_np(c),
+                                mass_coef=self.mass_coef, nquad=self.nquad)
 
     def _no_matrix(self, what):
         raise NotImplementedError(f"a matrix-free operator stores no coefficients: {what} is not available; "
@@ -191,10 +214,13 @@ class MatrixFreeVCycle(GalerkinVCycle):
 
     @classmethod
     def uniform(cls, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *, a=None, c=None,
-                mass_coef: float = 1.0, nquad: int | None = None, device=None, tol: float = 1e-6, maxiters=None):
+                mass_coef: float = 1.0, nquad: int | None = None, device=None, tol: float = 1e-6, maxiters=None,
+                mapping=None):
         """Dyadic uniform hierarchy, as :meth:`GalerkinVCycle.uniform`.  ``a`` / ``c``:
         None, scalars or callables (they are sampled on two quadrature grids, the
-        finest level's and level 1's)."""
+        finest level's and level 1's).  ``mapping``: the operator of the mapped domain
+        (:mod:`poms_amd.geometry`), its tensor sampled on those two grids; ``a`` / ``c``
+        are then functions of the physical coordinates."""
         for f in (a, c):
             if f is not None and not callable(f) and np.ndim(f) != 0:
                 raise ValueError("a / c must be None, scalars or callables here: they are sampled on two grids")
@@ -208,9 +234,14 @@ class MatrixFreeVCycle(GalerkinVCycle):
         knots = [uniform_knots(p, N) for N in cells]
         P1 = [two_level_setup_1d(p, knots[l], knots[l + 1])[2] for l in range(len(cells) - 1)]
         V = StencilVectorSpace([len(knots[0]) - p - 1] * ndim, [p] * ndim, device=device, align=True)
+        a1, c1 = a, c
+        if mapping is not None:
+            pull = lambda T: mapping.pullback([axis_tables(T, p, nquad)["points"].reshape(-1)] * ndim, a=a, c=c,
+                                              mass_coef=mass_coef, device=f"cuda:{V.device}")[:2]
+            (a, c), (a1, c1) = pull(knots[0]), pull(knots[1])
         A = MatrixFreeOperator(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef, nquad=nquad)
         V1 = StencilVectorSpace([len(knots[1]) - p - 1] * ndim, [p] * ndim, device=V.device, align=True)
-        A1 = assemble_stencil(V1, [knots[1]] * ndim, a=a, c=c, mass_coef=mass_coef, nquad=nquad)
+        A1 = assemble_stencil(V1, [knots[1]] * ndim, a=a1, c=c1, mass_coef=mass_coef, nquad=nquad)
         mg = cls(A, [[P1l] * ndim for P1l in P1], A1, tol=tol, maxiters=maxiters)
         mg.p, mg.ndim, mg.cells, mg.knots, mg.P1 = int(p), int(ndim), cells, knots, P1
         return mg

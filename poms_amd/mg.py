@@ -335,10 +335,13 @@ class GalerkinVCycle:
 
     @classmethod
     def uniform(cls, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *, a=None, c=None,
-                mass_coef: float = 1.0, device=None, tol: float = 1e-6, maxiters=None):
+                mass_coef: float = 1.0, device=None, tol: float = 1e-6, maxiters=None, mapping=None):
         """Dyadic uniform hierarchy (as :class:`MultilevelVCycle`'s) under
         ``-∇·(a∇u) + c u`` assembled on the finest knots by
-        :func:`~poms_amd.assembly.assemble_stencil`."""
+        :func:`~poms_amd.assembly.assemble_stencil`.  ``mapping`` (a
+        :class:`~poms_amd.geometry.Mapping` or ``SplineMapping``): the operator of the
+        mapped domain, its tensor sampled on the finest quadrature grid (``a`` / ``c``
+        are then functions of the physical coordinates)."""
         from .assembly import assemble_stencil
         if ncells_fine < ncells_coarsest or ncells_coarsest < 1:
             raise ValueError("need ncells_fine >= ncells_coarsest >= 1")
@@ -350,6 +353,10 @@ class GalerkinVCycle:
         knots = [uniform_knots(p, N) for N in cells]
         P1 = [two_level_setup_1d(p, knots[l], knots[l + 1])[2] for l in range(len(cells) - 1)]
         V = StencilVectorSpace([len(knots[0]) - p - 1] * ndim, [p] * ndim, device=device, align=True)
+        if mapping is not None:
+            from .assembly import axis_tables
+            pts = axis_tables(knots[0], p)["points"].reshape(-1)
+            a, c, _ = mapping.pullback([pts] * ndim, a=a, c=c, mass_coef=mass_coef, device=f"cuda:{V.device}")
         A = assemble_stencil(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef)
         mg = cls(A, [[P1l] * ndim for P1l in P1], tol=tol, maxiters=maxiters)
         mg.p, mg.ndim, mg.cells, mg.knots, mg.P1 = int(p), int(ndim), cells, knots, P1

@@ -21,10 +21,29 @@ size, its coefficients built as device tensors: cycle time, bytes held and the
 residual reduction over three cycles.
 
     python tools/matfree_bench.py [--out profiles/matfree/matfree_bench.json]
+
+``--tensor`` measures the tensor-coefficient operators instead, at the same
+shapes and with the same protocol, and writes ``profiles/tensor/tensor_bench.json``:
+
+* ``dot``, ``jacobi_sweep`` and ``dot_inner`` of the tensor ``MatrixFreeOperator`` and of
+  the stored tensor stencil, interleaved; the wall time of the assembly and of the
+  matrix-free set-up (tables and the diagonal kernel); the coefficients are built on the
+  device (``G = M M^T + I``);
+* the tensor ``dot`` against the scalar ``dot`` of this tree, next to the model's ratio
+  of stage C's work per point, (9 fma, ncomp + 1 loads) against (3 mul, 2 loads);
+* with ``--parent-lib PATH`` (a ``libpoms_hip.so`` built from the parent commit; the
+  package itself cannot load it through ``POMS_HIP_LIB``, it lacks the new entry points)
+  the scalar ``dot`` of this tree's library against the parent's, both called through
+  ``poms_op_apply`` on handles created from the same tables and arrays, taking turns
+  with a second handle of the parent's library, whose distance from the first is the
+  parent's own run-to-run spread.
+
+    python tools/matfree_bench.py --tensor [--parent-lib PATH] [--out profiles/tensor/tensor_bench.json]
 """
 from __future__ import annotations
 
 import argparse
+import ctypes as C
 import json
 import statistics
 import sys
@@ -61,6 +80,74 @@ def model(ndim, p, nq, tile=8):
     return per_dof, byt
 
 
+def m_coef(i, j, X):
+    """M_ij of the tensor mode's G = M M^T + I: smooth and distinct (torch, on the device)."""
+    arg = (i + 1.0) * X[0] + (2.0 * j + 1.0) * X[1] + ((i + j + 1.5) * X[2] if len(X) == 3 else 0.0)
+    return (0.3 + 0.1 * i + 0.05 * j) * torch.sin(arg + 0.5 * i - 0.3 * j)
+
+
+def tensor_model(ndim, p, nq, tile=8):
+    """The scalar model with stage C's scaling (4 Q^2 products per plane: w c u and
+    three w a d_i) replaced by the tensor's (w c u, and per flux 3 multiply-adds and the
+    product with w), and ncomp + 1 coefficient arrays instead of 2."""
+    flops, byt = model(ndim, p, nq, tile)
+    Q = (tile + p) * nq
+    nq0 = nq if ndim == 3 else 1
+    ncomp = ndim * (ndim + 1) // 2
+    flops += 2.0 * (3 * 3 * Q * Q) * nq0 / (tile * tile)
+    byt += 8.0 * (ncomp - 1) * nq ** ndim
+    return flops, byt
+
+
+class RawMatfree:
+    """A scalar matrix-free operator made and applied through the C entry points of a
+    given library (``poms_ctx_create``, ``poms_op_create_matfree``, ``poms_op_apply``):
+    the same calls whichever build the library is."""
+
+    def __init__(self, lib, V, knots, aq, cq):
+        from poms_amd import _lib
+        from poms_amd.assembly import axis_tables
+        for name in ("poms_ctx_create", "poms_ctx_destroy", "poms_op_create_matfree", "poms_op_apply",
+                     "poms_op_destroy"):
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = _lib._SIGS[name], C.c_int
+        lib.poms_last_error.restype = C.c_char_p
+        self.lib, self.V, self.keep = lib, V, [aq, cq]
+        nd = V.ndim
+        lead = 3 - nd
+        tabs = [axis_tables(np.asarray(T, float), V.pads[d]) for d, T in enumerate(knots)]
+
+        def arr3(key, dtype):
+            out = (C.c_void_p * 3)()
+            for k, t in enumerate(tabs):
+                a_ = np.ascontiguousarray(t[key], dtype=dtype)
+                self.keep.append(a_)
+                out[lead + k] = a_.ctypes.data
+            return out
+
+        ints = lambda key: (C.c_int * 3)(*([0] * lead + [int(t[key]) for t in tabs]))
+        self.ctx, self.h = C.c_void_p(), C.c_void_p()
+        self._ok(lib.poms_ctx_create(V.device, C.byref(self.ctx)))
+        self._ok(lib.poms_op_create_matfree(
+            self.ctx, nd, C.byref(V.layout), ints("nel"), ints("nq"), ints("p"), arr3("first", np.int32),
+            arr3("es", np.int32), arr3("ee", np.int32), arr3("basis", np.float64), arr3("weights", np.float64),
+            (C.c_int64 * 3)(*([1] * lead + [int(t["n"]) for t in tabs])), C.c_void_p(aq.data_ptr()),
+            C.c_void_p(cq.data_ptr()), 1.0, C.byref(self.h)))
+        self.n0 = int(V.npts[0]) if nd == 3 else 1
+
+    def _ok(self, status):
+        if status != 0:
+            raise RuntimeError(self.lib.poms_last_error().decode(errors="replace"))
+
+    def dot(self, x, y):
+        from poms_amd import runtime as rt
+        self._ok(self.lib.poms_op_apply(self.h, rt.ptr(x._data), rt.ptr(y._data), 0, self.n0, rt.stream_handle()))
+
+    def close(self):
+        self.lib.poms_op_destroy(self.h)
+        self.lib.poms_ctx_destroy(self.ctx)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--p", type=int, default=3)
@@ -73,6 +160,9 @@ def main() -> int:
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--probe-dots", type=int, default=0,
                     help="only build the 3D matrix-free operator and call dot this many times (for rocprofv3 runs)")
+    ap.add_argument("--tensor", action="store_true", help="measure the tensor-coefficient operators (DESIGN 3.15)")
+    ap.add_argument("--parent-lib", type=str, default=None,
+                    help="--tensor: a libpoms_hip.so of the parent commit for the scalar dot comparison")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError("matfree_bench needs a GPU: times are not taken on a CPU")
@@ -135,6 +225,83 @@ def main() -> int:
         torch.cuda.synchronize()
         return 0
     res = {"device": torch.cuda.get_device_name(0), "p": p, "reps": a.reps, "flush_mib": a.flush_mib, "configs": {}}
+    if a.tensor:
+        from poms_amd import _lib
+        parent = C.CDLL(a.parent_lib) if a.parent_lib else None
+        res["parent_lib"] = bool(parent)
+        for ndim, cells in ((3, a.cells3), (2, a.cells2)):
+            T = uniform_knots(p, cells)
+            V = StencilVectorSpace([cells + p] * ndim, [p] * ndim, align=True)
+            ndof = V.dimension
+            pts = torch.from_numpy(axis_tables(T, p)["points"].reshape(-1)).to(dev)
+            X = [pts.reshape([-1 if k == d else 1 for k in range(ndim)]) for d in range(ndim)]
+            M = [[m_coef(i, j, X) for j in range(ndim)] for i in range(ndim)]
+            G = torch.stack([torch.broadcast_to(sum(M[i][k] * M[j][k] for k in range(ndim)) + float(i == j),
+                                                (pts.numel(),) * ndim)
+                             for i in range(ndim) for j in range(i, ndim)]).contiguous()
+            aq = torch.broadcast_to((1.0 + 0.5 * torch.sin(3 * X[0]) * torch.cos(2 * X[1]))
+                                    * (1.0 + X[2] / 4 if ndim == 3 else 1.0), (pts.numel(),) * ndim).contiguous()
+            cq = torch.broadcast_to(2.0 + X[0] * X[1], (pts.numel(),) * ndim).contiguous()
+            del M
+            Amf, mf_ms, mf_held = built(lambda: MatrixFreeOperator(V, [T] * ndim, a=G, c=cq))
+            Ast, st_ms, st_held = built(lambda: assemble_stencil(V, [T] * ndim, a=G, c=cq))
+            Asc, sc_ms, _ = built(lambda: MatrixFreeOperator(V, [T] * ndim, a=aq, c=cq))
+            rng = np.random.default_rng(0)
+            x = V.zeros().from_numpy(rng.uniform(-1, 1, V.npts))
+            b = V.zeros().from_numpy(rng.uniform(-1, 1, V.npts))
+            y = V.zeros()
+            ref = Ast.dot(x)._data
+            diff = float((Amf.dot(x)._data - ref).abs().max() / ref.abs().max())
+            del ref
+            times = {}
+            for kind, call in (("dot", lambda A: A.dot(x, out=y)),
+                               ("jacobi_sweep", lambda A: A.jacobi_sweep(b, x, y, 2.0 / 3.0, want_norm=True, lazy=True)),
+                               ("dot_inner", lambda A: A.dot_inner(x, y, device=True))):
+                fns = {"matfree_tensor": lambda: call(Amf), "stencil_tensor": lambda: call(Ast)}
+                if kind == "dot":
+                    fns["matfree_scalar"] = lambda: call(Asc)
+                t = interleaved(fns)
+                t["matfree_over_stencil"] = t["matfree_tensor"]["ms"] / t["stencil_tensor"]["ms"]
+                times[kind] = t
+            fl_s, by_s = model(ndim, p, p + 1)
+            fl_t, by_t = tensor_model(ndim, p, p + 1)
+            ncomp = ndim * (ndim + 1) // 2
+            W = (2 * p + 1) ** ndim
+            cfg = {"cells": cells, "ndof": ndof, "maxrel_matfree_vs_stencil": diff, "times": times,
+                   "setup_ms": {"matfree_tensor_with_diagonal": mf_ms, "assemble_stencil_tensor": st_ms,
+                                "matfree_scalar_with_diagonal": sc_ms},
+                   "bytes_held": {"matfree_model": Amf.device_bytes(), "matfree_measured": mf_held,
+                                  "stencil_model": 8 * W * ndof, "stencil_measured": st_held,
+                                  "model_ratio": Amf.device_bytes() / (8.0 * W * ndof)},
+                   "tensor_over_scalar_dot": {
+                       "measured": times["dot"]["matfree_tensor"]["ms"] / times["dot"]["matfree_scalar"]["ms"],
+                       "stage_c_per_point": {"tensor": f"9 multiply-adds and 3 products with w, {ncomp + 1} loads",
+                                             "scalar": "w a and 3 products, 2 loads"},
+                       "model_flops_ratio": fl_t / fl_s, "model_bytes_ratio": by_t / by_s}}
+            if parent is not None:
+                mine = RawMatfree(_lib.lib, V, [T] * ndim, aq, cq)
+                par_a = RawMatfree(parent, V, [T] * ndim, aq, cq)
+                par_b = RawMatfree(parent, V, [T] * ndim, aq, cq)
+                y2 = V.zeros()
+                mine.dot(x, y)
+                par_a.dot(x, y2)
+                same = bool(torch.equal(y._data, y2._data))
+                t = interleaved({"parent_a": lambda: par_a.dot(x, y), "this_tree": lambda: mine.dot(x, y),
+                                 "parent_b": lambda: par_b.dot(x, y)})
+                lo = min(t["parent_a"]["min_ms"], t["parent_b"]["min_ms"])
+                hi = max(t["parent_a"]["max_ms"], t["parent_b"]["max_ms"])
+                t["bitwise_equal_to_parent"] = same
+                t["this_tree_median_within_parent_min_max"] = bool(lo <= t["this_tree"]["ms"] <= hi)
+                cfg["scalar_dot_vs_parent"] = t
+                for o in (mine, par_a, par_b):
+                    o.close()
+            res["configs"][f"{ndim}d_p{p}_{cells}"] = cfg
+            print(json.dumps({f"{ndim}d_p{p}_{cells}": cfg}), flush=True)
+            del Amf, Ast, Asc, G, aq, cq, x, b, y
+        out = a.out or "profiles/tensor/tensor_bench.json"
+        Path(out).parent.mkdir(parents=True, exist_ok=True)
+        Path(out).write_text(json.dumps(res) + "\n")
+        return 0
     for ndim, cells in ((3, a.cells3), (2, a.cells2)):
         T = uniform_knots(p, cells)
         V = StencilVectorSpace([cells + p] * ndim, [p] * ndim, align=True)
