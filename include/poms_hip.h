@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-#define POMS_ABI_VERSION 6 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor */
+#define POMS_ABI_VERSION 7 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
+                            * 7: poms_pcg_opts.n_pbuf, .pbuf */
 
 /* operator forms (see poms_op_create) */
 #define POMS_FORM_SINGLE 0 /* y = F0 (x) F1 (x) F2 x                                  */
@@ -619,6 +620,14 @@ typedef struct poms_pcg_opts {
                       * still runs s = psolve(A, r), s.r, beta and p = s + beta p there
                       * (`sources/solvers.py:117-124`) and returns without reading them.
                       * The same x and info, one preconditioner call less.             */
+    int n_pbuf;      /* (ABI 7) deferred x updates: n_pbuf >= 2 further vectors of the
+                      * operator's layout (zero ghosts, aliasing nothing else) let p_{k+1}
+                      * go to another buffer than p_k, and x += alpha_k p_k run as one pass
+                      * per up to n_pbuf iterations instead of one per iteration: the same
+                      * fma per term, the same x and info.  One rank without ghost data and
+                      * not in speculative mode; else, and with 0, x is updated every
+                      * iteration.  At most 15 are used.                                  */
+    double* const* pbuf;
 } poms_pcg_opts;
 typedef struct poms_pcg_info {
     int niter;

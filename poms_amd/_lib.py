@@ -42,7 +42,8 @@ class Layout(C.Structure):
 
 class PcgOpts(C.Structure):
     _fields_ = [("tol", C.c_double), ("maxiter", C.c_int), ("jtol", C.c_double), ("jmaxiter", C.c_int),
-                ("omega", C.c_double), ("prev", C.c_int), ("next", C.c_int), ("skip_tail", C.c_int)]
+                ("omega", C.c_double), ("prev", C.c_int), ("next", C.c_int), ("skip_tail", C.c_int),
+                ("n_pbuf", C.c_int), ("pbuf", C.POINTER(C.c_void_p))]   # (ABI 7; default 0 / NULL)
 
 
 class PcgInfo(C.Structure):

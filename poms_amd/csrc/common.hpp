@@ -131,6 +131,17 @@ struct AlphaFold {
     double* sc = nullptr;
     int sr = 0;                     // V_RUPD: slot of s.r
     int copy_sr = 0;
+    double* hist = nullptr;         // V_RUPD / V_RNORM: block 0 stores alpha here too (the deferred x pass)
+};
+
+// The deferred x pass (vec_xpass_launch): x = fma(alpha_j, p_j, x) for j = 0 .. n-1 in one
+// pass, the terms of up to kXPassMax pcg iterations whose p_j were kept.
+constexpr int kXPassMax = 16;
+struct XPassArgs {
+    const double* p[kXPassMax];
+    int n = 0;
+    int from_zero = 0;   // x starts as 0 instead of being read
+    int alt_last = 0;    // the last term as stop_update rounds it (pcg's early-stop branch)
 };
 
 // 2D Jacobi expressions shared by kron_v3_kernel and kron2d_j2_kernel, written with

@@ -34,7 +34,10 @@ int kron2d_j2_launch(int pmax, int form, const KronPtrs& p, const KronGeom& g, c
 // ---- vec_ops.hip ------------------------------------------------------------------
 enum VecOp : int { V_AXPBY = 0, V_SCALE = 1, V_FILL = 2, V_DOT = 3, V_PCGUPD = 4, V_RUPD = 5, V_XPUPD = 6,
                   V_SCALEDOT = 7 /* z = a x and z.z (flat kernel only) */,
-                  V_FINUPD = 8 /* pcg's last iteration, see stop_update */ };
+                  V_FINUPD = 8 /* pcg's last iteration, see stop_update */,
+                  // pcg's deferred x updates (flat kernel only; pcg_native.hip)
+                  V_PUPD = 9 /* z = x + b y: V_XPUPD's p into another buffer, its x untouched */,
+                  V_RNORM = 10 /* V_RUPD's r.r without the store of r */ };
 
 int vec_launch(int op, const RowGeom& g, double a, double b, const double* x, const double* y,
                double* z, double* w, const double* q, double* partial, hipStream_t st,
@@ -42,6 +45,9 @@ int vec_launch(int op, const RowGeom& g, double a, double b, const double* x, co
 int vec_flat_launch(int op, int64_t count, double a, double b, const double* x, const double* y,
                     double* z, double* w, const double* q, double* partial, hipStream_t st,
                     int* nblk_out, const double* ab = nullptr, const AlphaFold* af = nullptr);
+// x = fma(alpha[j], p_j, x) over `count` doubles for the n terms of `xa` (flat only; 1: the
+// pointers do not share their 16-B phase, nothing launched)
+int vec_xpass_launch(int64_t count, const XPassArgs& xa, const double* alpha, double* x, hipStream_t st);
 int zero_ghosts_launch(const RowGeom& g, double* z, hipStream_t st);
 int reduce_launch(const double* partial, int count, double* out, hipStream_t st, int accumulate = 0);
 int reduce_wide_launch(const double* partial, int count, double* out, hipStream_t st, int accumulate = 0);

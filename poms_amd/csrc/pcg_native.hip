@@ -30,13 +30,15 @@ enum { H_RR0 = 0, H_RR = 1, H_J0 = 2 /* 2 slots */, H_JN = 4 /* 2 slots */ };
 // an unwritten partial in a host region: a NaN payload no reduction produces
 constexpr uint64_t kPartUnset = 0x7ff8dead0000beefull;
 
-__global__ void pcg_scalars_kernel(double* sc, int mode) {
+// (hist: where the deferred x pass reads this iteration's alpha, PcgRun::xflush; or null)
+__global__ void pcg_scalars_kernel(double* sc, int mode, double* hist) {
     if (threadIdx.x != 0) return;
     if (mode == 0) {            // alpha = s.r / p.q; pairs [1, alpha] and [alpha, beta]
         const double a = sc[SC_SR] / sc[SC_PQ];
         sc[SC_ONE] = 1.0;
         sc[SC_ALPHA] = a;
         sc[SC_ALPHA2] = a;
+        if (hist != nullptr) hist[0] = a;
     } else {                    // beta = s.r / s.r_old; s.r_old <- s.r
         sc[SC_BETA] = sc[SC_SRN] / sc[SC_SR];
         sc[SC_SR] = sc[SC_SRN];
@@ -46,7 +48,8 @@ __global__ void pcg_scalars_kernel(double* sc, int mode) {
 // p.q from the apply + dot launch's per-block partials -- reduce_partials_kernel's
 // order, so the same bits -- and alpha from it, in one launch (one rank: saves the
 // one-block reduction launch per pcg iteration)
-__global__ void __launch_bounds__(256) pcg_alpha_kernel(const double* __restrict__ part, int count, double* sc) {
+__global__ void __launch_bounds__(256) pcg_alpha_kernel(const double* __restrict__ part, int count, double* sc,
+                                                        double* hist) {
     __shared__ double red[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < count; i += 256) s += part[i];
@@ -57,6 +60,7 @@ __global__ void __launch_bounds__(256) pcg_alpha_kernel(const double* __restrict
     sc[SC_ONE] = 1.0;
     sc[SC_ALPHA] = a;
     sc[SC_ALPHA2] = a;
+    if (hist != nullptr) hist[0] = a;
 }
 
 // s.r_new from the last damped-Jacobi sweep's per-block partials (reduce_partials_kernel's
@@ -103,7 +107,7 @@ struct PcgRun {
     int apd_alpha(const double* p, double* q) {
         if (comm || op->dot_base >= 0 || op->part_off != 0 || op->part_dst || general_form(op)) {
             if (run(EPI_APPLYDOT, p, q, p, nullptr, sc + SC_PQ) || allsum(sc + SC_PQ, 1)) return 1;
-            hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, st, sc, 0);
+            hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, st, sc, 0, hist_slot);
             POMS_HIP_CHECK(hipGetLastError());
             return 0;
         }
@@ -125,9 +129,9 @@ struct PcgRun {
         POMS_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    static bool fold_on() {   // POMS_ALPHA_FOLD=0: the one-block scalar kernels (tuning / A-B)
-        static const bool f = !(getenv("POMS_ALPHA_FOLD") && getenv("POMS_ALPHA_FOLD")[0] == '0');
-        return f;
+    static bool fold_on() {   // POMS_ALPHA_FOLD=0: the one-block scalar kernels (tuning / A-B; read per
+        const char* e = getenv("POMS_ALPHA_FOLD");   // launch: the tests run both in one process)
+        return !(e && e[0] == '0');
     }
     // beta folded into the x/p update: x += alpha p, p = s + beta p with beta from the
     // last sweep's x . rhs partials (dot_part); 1 if it cannot (the caller runs
@@ -156,9 +160,78 @@ struct PcgRun {
     int flush_alpha() {
         if (fix_sr()) return 1;
         if (!alpha_part) return 0;
-        hipLaunchKernelGGL(pcg_alpha_kernel, dim3(1), dim3(256), 0, st, alpha_part, (int)alpha_n, sc);
+        hipLaunchKernelGGL(pcg_alpha_kernel, dim3(1), dim3(256), 0, st, alpha_part, (int)alpha_n, sc, hist_slot);
         alpha_part = nullptr;
         POMS_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    // ---- deferred x updates (poms_pcg_opts.n_pbuf >= 2 on the flat path) ----
+    // x is only read after the call, so x += alpha_k p_k need not run every iteration:
+    // the p update writes p_{k+1} to another buffer (pupd), the terms alpha_k p_k wait in
+    // `pend` with alpha_k at hist()[i], and one x pass applies them in order with the same
+    // fma per term (xflush): the same bits, x read and written once per flush.
+    bool defer = false;
+    int64_t doff = 0, dcount = 0;      // the flat range: whole interior planes
+    double* dx = nullptr;              // the call's x
+    bool x_zero = false;               // x0 = None and no x pass yet: x is the zero nothing has written
+    const double* pend[kXPassMax] = {};
+    int npend = 0;
+    double* hist_slot = nullptr;       // where the kernel that forms this iteration's alpha also stores it
+    double* hist() { return sc + SC_N; }
+    int push_term(const double* p) {   // alpha_k p_k, alpha_k not formed yet
+        if (npend == kXPassMax && xflush(false)) return 1;
+        hist_slot = hist() + npend;
+        pend[npend++] = p + doff;
+        return 0;
+    }
+    bool is_pending(const double* p) const {
+        for (int j = 0; j < npend; ++j)
+            if (pend[j] == p + doff) return true;
+        return false;
+    }
+    // x = fma(alpha_j, p_j, x) over the pending terms; alt_last: the last one as the
+    // early-stop branch's V_AXPBY(1, x, alpha, p) rounds it
+    int xflush(bool alt_last) {
+        if (npend == 0) return 0;
+        XPassArgs xa;
+        for (int j = 0; j < npend; ++j) xa.p[j] = pend[j];
+        xa.n = npend;
+        xa.from_zero = x_zero ? 1 : 0;
+        xa.alt_last = alt_last ? 1 : 0;
+        if (vec_xpass_launch(dcount, xa, hist(), dx + doff, st)) {
+            set_error("pcg: deferred x pass not launched");
+            return 1;
+        }
+        POMS_HIP_CHECK(hipGetLastError());
+        npend = 0;
+        x_zero = false;
+        return 0;
+    }
+    // pn = s + beta p (V_XPUPD's p, x untouched): beta folded where xpupd_beta folds it,
+    // else from pcg_beta_kernel / pcg_scalars_kernel as the plain x/p update takes it
+    int pupd(const double* s, const double* p, double* pn, bool part) {
+        const int head = (reinterpret_cast<uintptr_t>(pn + doff) & 15) ? 1 : 0;
+        const int64_t nbp = std::max<int64_t>(1, ((dcount - head) / 2 + 1023) / 1024);
+        const bool fold = part && fold_on() && dot_part_n * nbp <= (int64_t)1 << 20;
+        if (fix_sr()) return 1;   // (beta reads s.r_old at sc[SC_SR])
+        AlphaFold bf;
+        if (fold) {
+            bf.part = dot_part;
+            bf.n = (int)dot_part_n;
+            bf.sc = sc;
+        } else if (part) {
+            hipLaunchKernelGGL(pcg_beta_kernel, dim3(1), dim3(256), 0, st, dot_part, (int)dot_part_n, sc);
+        } else {
+            hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, st, sc, 1, (double*)nullptr);
+        }
+        int nb = 0;
+        if (vec_flat_launch(V_PUPD, dcount, 0.0, 0.0, s + doff, p + doff, pn + doff, nullptr, nullptr, nullptr, st, &nb,
+                            sc + SC_ALPHA2, fold ? &bf : nullptr)) {
+            set_error("pcg: deferred p update not launched");
+            return 1;
+        }
+        POMS_HIP_CHECK(hipGetLastError());
+        if (fold) sr_stale = true;
         return 0;
     }
     // the last sweep of a psolve left x . rhs as per-block partials (dot_part, dot_part_n
@@ -379,7 +452,10 @@ struct PcgRun {
     // With x and p (skip_tail's last iteration): the final pass instead -- x += alpha p as
     // well, r - alpha q not kept (V_FINUPD); the same count, head, grid and per-thread
     // order, so the partials and r.r are the r update's bits.
-    int rupd(double* r, const double* q, int h, double* x = nullptr, const double* p = nullptr) {
+    // norm_only (the deferred loop's last iteration under skip_tail): the sum alone
+    // (V_RNORM), r and x untouched -- the x pass follows once the stop test is known.
+    int rupd(double* r, const double* q, int h, double* x = nullptr, const double* p = nullptr,
+             bool norm_only = false) {
         if (direct() && !(op->L.flags & POMS_LAYOUT_GHOST_DATA)) {
             const RowGeom g = row_geom(&op->L);
             const int64_t off = (int64_t)g.pd0 * g.s0, count = (int64_t)g.n0 * g.s0;
@@ -392,21 +468,22 @@ struct PcgRun {
                 // partials are small (2D: 468 partials x ~515 blocks; not the 3D grid's
                 // 495 x 65536): one launch less per pcg iteration (round 6)
                 AlphaFold af;
-                static const bool fold = !(getenv("POMS_ALPHA_FOLD") && getenv("POMS_ALPHA_FOLD")[0] == '0');
+                const bool fold = fold_on();
                 if (fold && alpha_part && alpha_n * nbp <= (int64_t)1 << 20) {
                     af.part = alpha_part;
                     af.n = (int)alpha_n;
                     af.sc = sc;
                     af.sr = sr_stale ? SC_SRN : SC_SR;   // (a folded beta's s.r_new, copied to SC_SR by block 0)
                     af.copy_sr = sr_stale ? 1 : 0;
+                    af.hist = hist_slot;
                     static_assert(SC_SR == 0 && SC_PQ == 1 && SC_ONE == 2 && SC_ALPHA == 3 && SC_ALPHA2 == 4,
                                   "AlphaFold's slots");
                 } else if (flush_alpha()) {
                     return 1;
                 }
-                if (vec_flat_launch(x ? V_FINUPD : V_RUPD, count, 0.0, 0.0, nullptr, x ? p + off : nullptr,
-                                    x ? x + off : nullptr, r + off, q + off, reg, st, &nb, sc + SC_ALPHA,
-                                    af.part ? &af : nullptr) == 0) {
+                const int vop = norm_only ? V_RNORM : x ? V_FINUPD : V_RUPD;
+                if (vec_flat_launch(vop, count, 0.0, 0.0, nullptr, x ? p + off : nullptr, x ? x + off : nullptr,
+                                    r + off, q + off, reg, st, &nb, sc + SC_ALPHA, af.part ? &af : nullptr) == 0) {
                     if (af.part) sr_stale = false;
                     alpha_part = nullptr;
                     POMS_HIP_CHECK(hipGetLastError());
@@ -419,6 +496,17 @@ struct PcgRun {
         if (flush_alpha()) return 1;
         double* d = hslot(h);
         if (!d) return 1;
+        if (norm_only) {   // (deferred: one rank, the flat kernel applies) as vec_common reduces V_RUPD's partials
+            int nb = 0;
+            if (vec_flat_launch(V_RNORM, dcount, 0.0, 0.0, nullptr, nullptr, nullptr, r + doff, q + doff,
+                                op->ctx->scratch, st, &nb, sc + SC_ALPHA)) {
+                set_error("pcg: norm-only r pass not launched");
+                return 1;
+            }
+            reduce_wide_launch(op->ctx->scratch, nb, d, st);
+            POMS_HIP_CHECK(hipGetLastError());
+            return 0;
+        }
         if (x ? poms_pcg_final_update_dev(op->ctx, &op->L, sc + SC_ALPHA, x, p, r, q, d, stv)
               : poms_pcg_r_update_dev(op->ctx, &op->L, sc + SC_ALPHA, r, q, d, stv))
             return 1;
@@ -713,7 +801,7 @@ static int spec_issue(PcgRun& R, const double* b, double* x, int has_x0, double*
         if (c != p) (fa ? fb : fa) = c;
     for (int k = 1; k <= o->maxiter; ++k) {
         if (R.run(EPI_APPLYDOT, p, q, p, nullptr, R.sc + SC_PQ) || R.allsum(R.sc + SC_PQ, 1)) return 1;
-        hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 0);
+        hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 0, (double*)nullptr);
         const int vrr = R.svals(1);
         R.srr.push_back(vrr);
         if (o->skip_tail && k == o->maxiter) {   // the rest of this iteration is discarded
@@ -723,7 +811,7 @@ static int spec_issue(PcgRun& R, const double* b, double* x, int has_x0, double*
         if (poms_pcg_r_update_dev(ctx, L, R.sc + SC_ALPHA, r, q, op->spec_dev + vrr, stream)) return 1;
         double* sn = nullptr;
         if (R.spec_damped_jacobi(r, fa, fb, SC_SRN, &sn)) return 1;
-        hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 1);
+        hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 1, (double*)nullptr);
         if (poms_pcg_xp_update_dev(ctx, L, R.sc + SC_ALPHA2, x, p, sn, stream)) return 1;
     }
     if (R.sn > poms_op::kSpecVals) { set_error("pcg speculative: too many values"); return 1; }
@@ -898,8 +986,9 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
     if (o->maxiter < 0 || o->jmaxiter < 1) { set_error("poms_pcg_jacobi: bad iteration counts"); return 1; }
     POMS_HIP_CHECK(hipSetDevice(op->ctx->device));
     if (!op->sv_dev) {
-        POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->sv_dev), SC_N * sizeof(double)));
-        POMS_HIP_CHECK(hipMemset(op->sv_dev, 0, SC_N * sizeof(double)));
+        // (the scalars, then the deferred x pass's alpha_hist[kXPassMax])
+        POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->sv_dev), (SC_N + kXPassMax) * sizeof(double)));
+        POMS_HIP_CHECK(hipMemset(op->sv_dev, 0, (SC_N + kXPassMax) * sizeof(double)));
         // coherent (fine-grained) and device-mapped: reduction kernels write the
         // host-read norms straight into it
         POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&op->sv_host), poms_op::kSvRing * sizeof(double),
@@ -942,9 +1031,27 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
     const poms_layout* L = &op->L;
     double *r = work[0], *q = work[1];
     double* z[3] = {work[2], work[3], work[4]};
-    // x0 = None: x = 0, r = b - A.0 = b exactly; else r = b - A x0
+    // Deferred x updates: p buffers passed, the flat path (one rank, no ghost data, every
+    // vector on one 16-B phase); not after a speculative attempt (that mode keeps the
+    // per-iteration updates, and so does its step-by-step repeat)
+    const int npb = std::min<int>(o->n_pbuf, kXPassMax - 1);   // (p_1 and npb more terms fill one x pass)
+    if (npb >= 2 && o->pbuf && o->maxiter >= 1 && R.direct() && !(op->L.flags & POMS_LAYOUT_GHOST_DATA) &&
+        !pcg_spec_wanted(op, o)) {
+        const RowGeom g = row_geom(&op->L);
+        R.doff = (int64_t)g.pd0 * g.s0;
+        R.dcount = (int64_t)g.n0 * g.s0;
+        R.dx = x;
+        const uintptr_t ph = reinterpret_cast<uintptr_t>(x) & 15;
+        bool ok = R.dcount >= 4 && (ph & 7) == 0;
+        for (int i = 0; i < 5; ++i) ok = ok && (reinterpret_cast<uintptr_t>(work[i]) & 15) == ph;
+        for (int i = 0; i < npb; ++i) ok = ok && o->pbuf[i] && (reinterpret_cast<uintptr_t>(o->pbuf[i]) & 15) == ph;
+        R.defer = ok;
+    }
+    R.x_zero = R.defer && !has_x0;
+    // x0 = None: x = 0 (deferred: the first x pass starts from zero instead), r = b - A.0 = b
+    // exactly; else r = b - A x0
     if (!has_x0) {
-        if (poms_vec_fill(ctx, L, 0.0, x, stream)) return 1;
+        if (!R.defer && poms_vec_fill(ctx, L, 0.0, x, stream)) return 1;
     } else if (R.run(EPI_RESID, x, r, b, nullptr, nullptr)) {
         return 1;
     }
@@ -1004,10 +1111,22 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
     double* fb = fp[1];
     double* fc = fp[2];   // (nullptr without the lookahead)
     int k = 0;
+    int pring = 0;   // deferred: the p buffer p_{k+1} goes to
     double nrmr = nrmr0 * nrmr0;
     for (k = 1; k <= o->maxiter; ++k) {
+        if (R.defer && R.push_term(p)) return 1;   // (before the launch that forms alpha_k)
         if (R.apd_alpha(p, q)) return 1;
         const int hrr = R.arm(H_RR, 1);
+        if (R.defer && o->skip_tail && k == o->maxiter) {
+            // the sum alone, then x with the rounding the stop test selects
+            if (R.rupd(r, q, hrr, nullptr, nullptr, true)) return 1;
+            nrmr = R.get(hrr);
+            if (R.failed) return 1;
+            const bool stop = nrmr < o->tol * nrmr0;
+            if (R.xflush(stop)) return 1;
+            if (stop) k -= 1;
+            break;
+        }
         if (o->skip_tail && k == o->maxiter) {
             // the reference goes on to s = psolve(A, r), s.r, beta and p (`sources/solvers.py:117-124`)
             // and returns without reading any of them: x and r.r only
@@ -1027,9 +1146,17 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
         nrmr = R.get(hrr);
         if (R.failed) return 1;
         if (nrmr < o->tol * nrmr0) {   // the reference stops before psolve: that one is discarded
-            if (poms_vec_axpby_dev(ctx, L, R.sc + SC_ONE, x, p, x, stream)) return 1;
+            if (R.defer ? R.xflush(true) : poms_vec_axpby_dev(ctx, L, R.sc + SC_ONE, x, p, x, stream)) return 1;
             k -= 1;
             break;
+        }
+        if (R.defer) {   // p_{k+1} into the next p buffer; x first where that one still holds a pending term
+            double* pn = o->pbuf[pring];
+            if (R.is_pending(pn) && R.xflush(false)) return 1;
+            if (R.pupd(sn, p, pn, dd && R.dot_part_n >= 0)) return 1;
+            p = pn;
+            pring = (pring + 1) % npb;
+            continue;
         }
         // beta folded into the x/p update where it can be (one rank, small grids)
         const int fb = (dd && R.dot_part_n >= 0) ? R.xpupd_beta(x, p, sn) : 1;
@@ -1039,7 +1166,7 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
             if (dd && R.dot_part_n >= 0)   // x . rhs's partials from the last sweep, reduced here
                 hipLaunchKernelGGL(pcg_beta_kernel, dim3(1), dim3(256), 0, R.st, R.dot_part, (int)R.dot_part_n, R.sc);
             else
-                hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 1);
+                hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 1, (double*)nullptr);
             if (poms_pcg_xp_update_dev(ctx, L, R.sc + SC_ALPHA2, x, p, sn, stream)) return 1;
         }
     }
@@ -1047,6 +1174,9 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
     // psolve writes s.r before anything reads it)
     R.sr_stale = false;
     if (R.flush_alpha()) return 1;
+    // deferred: the terms still pending when the loop ran out (maxiter >= 1: from x0 = None
+    // at least one x pass has run by now, x is written)
+    if (R.defer && R.xflush(false)) return 1;
     if (k > o->maxiter) k = o->maxiter;
     info->niter = k;
     info->success = nrmr < o->tol * nrmr0 ? 1 : 0;

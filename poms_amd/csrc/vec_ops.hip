@@ -111,6 +111,11 @@ __device__ __forceinline__ void vec_elem(double a, double b, const double* x, co
         const double rn = fma(-a, q[o], w[o]);
         w[o] = rn;
         s = fma(rn, rn, s);
+    } else if constexpr (OP == V_RNORM) {
+        const double rn = fma(-a, q[o], w[o]);
+        s = fma(rn, rn, s);
+    } else if constexpr (OP == V_PUPD) {
+        z[o] = x[o] + b * yv[o];
     } else if constexpr (OP == V_FINUPD) {
         const double xo = z[o], po = yv[o];
         z[o] = fma(a, po, xo);
@@ -138,14 +143,14 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
     typedef double d2 __attribute__((ext_vector_type(2)));
     constexpr int U = 4;
     __shared__ double red[4];
-    if constexpr (OP == V_RUPD || OP == V_XPUPD || OP == V_FINUPD) {
+    if constexpr (OP == V_RUPD || OP == V_XPUPD || OP == V_FINUPD || OP == V_PUPD || OP == V_RNORM) {
         if (af.part != nullptr) {   // alpha / beta from partials (see AlphaFold)
             double sp = 0.0;
             for (int i = threadIdx.x; i < af.n; i += 256) sp += af.part[i];
             const double t = block_sum_256(sp, red);
             if (threadIdx.x == 0) {
                 double v;
-                if constexpr (OP != V_XPUPD) {   // t = p.q
+                if constexpr (OP != V_XPUPD && OP != V_PUPD) {   // t = p.q
                     v = af.sc[af.sr] / t;
                     if (blockIdx.x == 0) {
                         af.sc[1] = t;
@@ -153,6 +158,7 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
                         af.sc[3] = v;
                         af.sc[4] = v;
                         if (af.copy_sr) af.sc[0] = af.sc[af.sr];
+                        if (af.hist != nullptr) af.hist[0] = v;
                     }
                 } else {                        // t = s.r_new
                     v = t / af.sc[0];
@@ -164,7 +170,7 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
                 red[0] = v;
             }
             __syncthreads();
-            if constexpr (OP != V_XPUPD) a = red[0];
+            if constexpr (OP != V_XPUPD && OP != V_PUPD) a = red[0];
             else b = red[0];
             __syncthreads();   // (red is the final reduction's again)
         }
@@ -186,12 +192,15 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
                 // (tools/ubench_copy.hip: 1 KiB per wave and load, nt loads + nt stores
                 // 6.1-6.2 TB/s against 5.7 with plain loads)
                 auto ld = [](const d2* ptr) { if constexpr (NTL) return __builtin_nontemporal_load(ptr); else return *ptr; };
-                if constexpr (OP == V_AXPBY || OP == V_SCALE || OP == V_DOT || OP == V_XPUPD || OP == V_SCALEDOT)
+                if constexpr (OP == V_AXPBY || OP == V_SCALE || OP == V_DOT || OP == V_XPUPD || OP == V_SCALEDOT ||
+                              OP == V_PUPD)
                     xa[u] = ld(X + i);
-                if constexpr (OP == V_AXPBY || OP == V_DOT || OP == V_PCGUPD || OP == V_FINUPD) ya[u] = ld(Y + i);
+                if constexpr (OP == V_AXPBY || OP == V_DOT || OP == V_PCGUPD || OP == V_FINUPD || OP == V_PUPD)
+                    ya[u] = ld(Y + i);
                 if constexpr (OP == V_PCGUPD || OP == V_XPUPD || OP == V_FINUPD) za[u] = ld(Z + i);
-                if constexpr (OP == V_PCGUPD || OP == V_RUPD || OP == V_XPUPD || OP == V_FINUPD) wa[u] = ld(Wv + i);
-                if constexpr (OP == V_PCGUPD || OP == V_RUPD || OP == V_FINUPD) qa[u] = ld(Q + i);
+                if constexpr (OP == V_PCGUPD || OP == V_RUPD || OP == V_XPUPD || OP == V_FINUPD || OP == V_RNORM)
+                    wa[u] = ld(Wv + i);
+                if constexpr (OP == V_PCGUPD || OP == V_RUPD || OP == V_FINUPD || OP == V_RNORM) qa[u] = ld(Q + i);
             }
         }
 #pragma unroll
@@ -225,6 +234,17 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
                     __builtin_nontemporal_store(rn, Wv + i);
                     s = fma(rn.x, rn.x, s);
                     s = fma(rn.y, rn.y, s);
+                } else if constexpr (OP == V_RNORM) {   // V_RUPD's sum, no store
+                    d2 rn;
+                    rn.x = fma(-a, qa[u].x, wa[u].x);
+                    rn.y = fma(-a, qa[u].y, wa[u].y);
+                    s = fma(rn.x, rn.x, s);
+                    s = fma(rn.y, rn.y, s);
+                } else if constexpr (OP == V_PUPD) {    // V_XPUPD's p, into z
+                    d2 wn;
+                    wn.x = xa[u].x + b * ya[u].x;
+                    wn.y = xa[u].y + b * ya[u].y;
+                    __builtin_nontemporal_store(wn, Z + i);
                 } else if constexpr (OP == V_FINUPD) {   // x as V_XPUPD's, the sum as V_RUPD's
                     d2 zn, rn, wn;
                     zn.x = fma(a, ya[u].x, za[u].x);
@@ -253,9 +273,73 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
         if (head) vec_elem<OP>(a, b, x, yv, z, w, q, 0, s);
         if (tail) vec_elem<OP>(a, b, x, yv, z, w, q, head + 2 * nd2, s);
     }
-    if constexpr (OP == V_DOT || OP == V_PCGUPD || OP == V_RUPD || OP == V_SCALEDOT || OP == V_FINUPD) {
+    if constexpr (OP == V_DOT || OP == V_PCGUPD || OP == V_RUPD || OP == V_SCALEDOT || OP == V_FINUPD ||
+                  OP == V_RNORM) {
         const double t = block_sum_256(s, red);
         if (threadIdx.x == 0) partial[blockIdx.x] = t;
+    }
+}
+
+// The deferred x pass of pcg's native loop: x = fma(alpha_j, p_j, x) for j = 0 .. N-1, the
+// chain of V_XPUPD's x updates of N iterations with x held in a register, so x is read
+// (not at all from zero) and written once for N terms.  Term by term the same fma, so the
+// same bits; the last term optionally as stop_update rounds it.  Flat range, head / tail
+// and 16-B accesses as vec_flat_kernel; every p_j and x streamed once (non-temporal).
+constexpr int kXPassU = 2;
+static_assert(kXPassMax == 16, "vec_xpass_launch instantiates N = 1 .. 16");
+
+template <int N, bool NTL>
+__global__ void __launch_bounds__(256)
+vec_xpass_kernel(const int head, const int64_t nd2, const int tail, const XPassArgs xa,
+                 const double* __restrict__ alpha, double* __restrict__ x) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    constexpr int U = kXPassU;
+    double al[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) al[j] = alpha[j];
+    const bool zero = xa.from_zero != 0, alt = xa.alt_last != 0;
+    d2* X = (d2*)(x + head);
+    auto ld = [](const d2* ptr) { if constexpr (NTL) return __builtin_nontemporal_load(ptr); else return *ptr; };
+    const int64_t step = (int64_t)gridDim.x * 256 * U;
+    for (int64_t base = (int64_t)blockIdx.x * 256 * U + threadIdx.x; base < nd2; base += step) {
+        d2 xv[U], pv[N][U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = base + u * 256;
+            if (i < nd2) {
+                xv[u] = zero ? d2{0.0, 0.0} : ld(X + i);
+#pragma unroll
+                for (int j = 0; j < N; ++j) pv[j][u] = ld((const d2*)(xa.p[j] + head) + i);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = base + u * 256;
+            if (i < nd2) {
+                d2 v = xv[u];
+#pragma unroll
+                for (int j = 0; j < N - 1; ++j) {
+                    v.x = fma(al[j], pv[j][u].x, v.x);
+                    v.y = fma(al[j], pv[j][u].y, v.y);
+                }
+                d2 f, t;
+                f.x = fma(al[N - 1], pv[N - 1][u].x, v.x);
+                f.y = fma(al[N - 1], pv[N - 1][u].y, v.y);
+                t.x = stop_update(al[N - 1], pv[N - 1][u].x, v.x);
+                t.y = stop_update(al[N - 1], pv[N - 1][u].y, v.y);
+                __builtin_nontemporal_store(alt ? t : f, X + i);
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (int e = 0; e < 2; ++e) {
+            if (!(e == 0 ? head : tail)) continue;
+            const int64_t o = e == 0 ? 0 : head + 2 * nd2;
+            double v = zero ? 0.0 : x[o];
+#pragma unroll
+            for (int j = 0; j < N - 1; ++j) v = fma(al[j], xa.p[j][o], v);
+            x[o] = alt ? stop_update(al[N - 1], xa.p[N - 1][o], v) : fma(al[N - 1], xa.p[N - 1][o], v);
+        }
     }
 }
 
@@ -441,7 +525,10 @@ int zero_ghosts_launch(const RowGeom& g, double* z, hipStream_t st) {
 int vec_flat_launch(int op, int64_t count, double a, double b, const double* x, const double* y,
                     double* z, double* w, const double* q, double* partial, hipStream_t st,
                     int* nblk_out, const double* ab, const AlphaFold* af) {
-    const AlphaFold afv = (af != nullptr && (op == V_RUPD || op == V_XPUPD || op == V_FINUPD)) ? *af : AlphaFold{};
+    const AlphaFold afv = (af != nullptr && (op == V_RUPD || op == V_XPUPD || op == V_FINUPD || op == V_PUPD ||
+                                             op == V_RNORM))
+                              ? *af
+                              : AlphaFold{};
     if (op == V_FILL || count < 4) return 1;
     int mis = -1;
     for (const void* ptr : {(const void*)x, (const void*)y, (const void*)z, (const void*)w, (const void*)q}) {
@@ -486,7 +573,42 @@ int vec_flat_launch(int op, int64_t count, double a, double b, const double* x, 
         POMS_VF(V_XPUPD)
         POMS_VF(V_SCALEDOT)
         POMS_VF(V_FINUPD)
+        POMS_VF(V_PUPD)
+        POMS_VF(V_RNORM)
 #undef POMS_VF
+    }
+    return 1;
+}
+
+int vec_xpass_launch(int64_t count, const XPassArgs& xa, const double* alpha, double* x, hipStream_t st) {
+    if (count < 4 || xa.n < 1 || xa.n > kXPassMax || !alpha || !x) return 1;
+    const int mis = (int)(reinterpret_cast<uintptr_t>(x) & 15);
+    if (mis & 7) return 1;
+    for (int j = 0; j < xa.n; ++j)
+        if (!xa.p[j] || (int)(reinterpret_cast<uintptr_t>(xa.p[j]) & 15) != mis) return 1;
+    const int head = mis ? 1 : 0;
+    const int64_t nd2 = (count - head) / 2;
+    const int tail = (int)((count - head) - 2 * nd2);
+    int64_t nb = (nd2 + 256 * kXPassU - 1) / (256 * kXPassU);
+    if (nb > ((int64_t)1 << 20)) nb = (int64_t)1 << 20;   // (grid-stride beyond)
+    if (nb < 1) nb = 1;
+    static const bool plain = [] {
+        const char* e = getenv("POMS_VEC_LOADS");
+        return e && e[0] == 'p';
+    }();
+    switch (xa.n) {
+#define POMS_XP(NV)                                                                                            \
+    case NV:                                                                                                   \
+        if (plain)                                                                                             \
+            hipLaunchKernelGGL((vec_xpass_kernel<NV, false>), dim3((int)nb), dim3(256), 0, st, head, nd2, tail, xa, \
+                               alpha, x);                                                                      \
+        else                                                                                                   \
+            hipLaunchKernelGGL((vec_xpass_kernel<NV, true>), dim3((int)nb), dim3(256), 0, st, head, nd2, tail, xa, \
+                               alpha, x);                                                                      \
+        return 0;
+        POMS_XP(1) POMS_XP(2) POMS_XP(3) POMS_XP(4) POMS_XP(5) POMS_XP(6) POMS_XP(7) POMS_XP(8)
+        POMS_XP(9) POMS_XP(10) POMS_XP(11) POMS_XP(12) POMS_XP(13) POMS_XP(14) POMS_XP(15) POMS_XP(16)
+#undef POMS_XP
     }
     return 1;
 }

@@ -40,7 +40,7 @@ import torch
 from . import _lib
 from . import runtime as rt
 from .multilevels import KronTransfer, knots_to_insert
-from .solvers import damped_jacobi, pcg
+from .solvers import damped_jacobi, defer_x_count, pcg
 from .splines import assemble_1d, matrix_multi_stages, uniform_knots
 from .stencil import F64, KronOperator, StencilVector, StencilVectorSpace
 
@@ -143,7 +143,10 @@ class TwoLevelVCycle:
         """One V-cycle; returns ``(xf2, info_pre, info_pos)``."""
         A = self.A
         # (_skip_tail: a smoother call's last iteration ends at x and r.r, see solvers.pcg)
-        xf, info_pre = pcg(A, damped_jacobi, bf, x0=x0, tol=self.tol, maxiter=self.maxiter, _skip_tail=True)
+        # (_defer_x: x brought up to date once per call where that pays, see solvers.defer_x_count)
+        dx = defer_x_count(A, self.space, self.maxiter)
+        xf, info_pre = pcg(A, damped_jacobi, bf, x0=x0, tol=self.tol, maxiter=self.maxiter, _skip_tail=True,
+                           _defer_x=dx)
         if self.fused_restrict:
             rc = self.transfer.resid_restrict(A, bf, xf, out=self.rc)
         else:
@@ -158,7 +161,7 @@ class TwoLevelVCycle:
         else:
             # (xf is this cycle's own temporary: iterate in its buffer, no copy)
             xf2, info_pos = pcg(A, damped_jacobi, bf, x0=xf, tol=self.tol, maxiter=self.maxiter, _x0_owned=True,
-                                _skip_tail=True)
+                                _skip_tail=True, _defer_x=dx)
         return xf2, info_pre, info_pos
 
 
@@ -257,7 +260,9 @@ class MultilevelVCycle:
 
     def _level(self, l: int, b: StencilVector, x0: StencilVector | None) -> StencilVector:
         A, tr = self.ops[l], self.transfers[l]
-        x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True)
+        dx = defer_x_count(A, self.spaces[l], self.maxiters[l])
+        x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True,
+                      _defer_x=dx)
         if self.fused[l]:
             rc = tr.resid_restrict(A, b, x, out=self.rcs[l])
         else:
@@ -276,7 +281,8 @@ class MultilevelVCycle:
             ec = Vc.interior(ecv._data).contiguous().view(-1)
         tr.prolong_add(ec, x)
         x.update_ghost_regions()
-        x, ipos = pcg(A, damped_jacobi, b, x0=x, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True)
+        x, ipos = pcg(A, damped_jacobi, b, x0=x, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True,
+                      _defer_x=dx)
         if self.infos[l] is None:
             self.infos[l] = (ipre, ipos)
         return x
@@ -384,7 +390,9 @@ class GalerkinVCycle:
 
     def _level(self, l: int, b: StencilVector, x0: StencilVector | None) -> StencilVector:
         A, tr = self.ops[l], self.transfers[l]
-        x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True)
+        dx = defer_x_count(A, self.spaces[l], self.maxiters[l])
+        x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True,
+                      _defer_x=dx)
         rc = tr.restrict(A.residual(b, x), out=self.rcs[l])
         if l + 1 == self.nlevels - 1:
             ec = self.xc
@@ -400,7 +408,8 @@ class GalerkinVCycle:
             ec = Vc.interior(ecv._data).contiguous().view(-1)
         tr.prolong_add(ec, x)
         x.update_ghost_regions()
-        x, ipos = pcg(A, damped_jacobi, b, x0=x, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True)
+        x, ipos = pcg(A, damped_jacobi, b, x0=x, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True,
+                      _defer_x=dx)
         if self.infos[l] is None:
             self.infos[l] = (ipre, ipos)
         return x

@@ -21,6 +21,8 @@ Differences that do not change results:
 * the reference's discarded ``s = A.dot(r)`` (:109) is not computed;
 * with ``_skip_tail`` (the V-cycles' smoother calls) neither are ``psolve``, ``s.r``,
   ``beta`` and ``p`` of iteration ``k == maxiter`` (:117-124), which nothing reads;
+* with ``_defer_x`` (the 3D V-cycles' smoother calls) ``x += alpha p`` of several
+  iterations runs as one pass over their kept ``p`` (the same fma per term: the same bits);
 * the per-element Python loop ``dr = omega*r/A[i,i,0,0]`` (:211-213) and the
   surrounding ``r = b - A.dot(x)``, ``x = x + dr``, ``dr.dot(dr)`` are one
   fused HIP kernel; the first sweep from ``x0 = None`` uses ``A.0 = 0``
@@ -68,7 +70,8 @@ def _tail_skipped(skip_tail) -> bool:
     return bool(skip_tail) and os.environ.get("POMS_PCG_TAIL", "0") != "1"
 
 
-def pcg(A, psolve, b, x0=None, tol=1e-6, maxiter=100, verbose=False, *, _x0_owned=False, _skip_tail=False):
+def pcg(A, psolve, b, x0=None, tol=1e-6, maxiter=100, verbose=False, *, _x0_owned=False, _skip_tail=False,
+        _defer_x=0):
     """Preconditioned conjugate gradient (`sources/solvers.py:69-135`).
 
     ``_skip_tail`` (internal: the V-cycles' smoother calls): iteration ``k == maxiter``
@@ -79,14 +82,20 @@ def pcg(A, psolve, b, x0=None, tol=1e-6, maxiter=100, verbose=False, *, _x0_owne
 
     ``_x0_owned`` (internal: the V-cycle's own temporaries) lets the native loop
     iterate in x0's buffer instead of a copy of it -- the reference copies x0
-    (`sources/solvers.py:82`); a caller that never reads x0 again loses nothing."""
+    (`sources/solvers.py:82`); a caller that never reads x0 again loses nothing.
+
+    ``_defer_x`` (internal: the 3D V-cycles' smoother calls, see :func:`defer_x_count`):
+    the number of extra ``p`` buffers the native loop may keep, so that ``x += alpha p``
+    runs as one pass per that many iterations instead of one per iteration -- the same
+    fma per term, the same ``x`` and ``info``; one more vector of memory per buffer.
+    ``POMS_PCG_DEFER_X=<n>`` (read per call) replaces a non-zero count, 0 turns it off."""
     _check(A, b)
     V = b.space
     skip_tail = _tail_skipped(_skip_tail)
     if (psolve is damped_jacobi and not verbose and V.lazy_reductions and A.apply_dot_supported
             and A.fused_dot_supported):
         if _native_ok(A, V):
-            return _pcg_native(A, b, x0, tol, maxiter, _x0_owned, skip_tail)
+            return _pcg_native(A, b, x0, tol, maxiter, _x0_owned, skip_tail, _defer_x)
         return _pcg_device(A, b, x0, tol, maxiter, skip_tail)
     ctx, lay = V.ctx, V.layout
     if x0 is None:
@@ -209,7 +218,42 @@ def _native_ok(A, V) -> bool:
     return not V.is_distributed or V.dist.native is not None
 
 
-def _pcg_native(A, b, x0, tol, maxiter, x0_owned=False, skip_tail=False):
+def defer_x_count(A, V, maxiter) -> int:
+    """The ``_defer_x`` a V-cycle passes to its smoother calls: ``min(maxiter, 10)`` p
+    buffers on a 3D single-rank space whose pcg runs natively, else 0.  (In 2D the vectors
+    live in the cache, the loop is latency-bound and beta is folded: nothing to gain.)"""
+    if V.ndim != 3 or V.is_distributed or not _native_ok(A, V):
+        return 0
+    return max(0, min(int(maxiter), 10))
+
+
+def _defer_buffers(A, V, n):
+    """``n`` p buffers for the deferred x updates, allocated lazily, once, beside
+    ``A._pcg_work`` (every smoother call on A shares them); [] when ``n`` < 2, when
+    ``POMS_PCG_DEFER_X`` says 0, or when the allocation fails (said once)."""
+    e = os.environ.get("POMS_PCG_DEFER_X", "")
+    if n and e != "":
+        n = int(e)
+    if n < 2 or getattr(A, "_pcg_defer_failed", False):
+        return []
+    n = min(n, 15)
+    bufs = getattr(A, "_pcg_pbufs", None)
+    if bufs is None or (bufs and bufs[0].space is not V):
+        bufs = A._pcg_pbufs = []
+    try:
+        while len(bufs) < n:
+            bufs.append(V.empty())
+    except RuntimeError as exc:   # (torch.cuda.OutOfMemoryError is one)
+        import warnings
+        A._pcg_pbufs = []
+        A._pcg_defer_failed = True
+        warnings.warn(f"pcg: no memory for {n} deferred-x buffers ({exc.__class__.__name__}); "
+                      "x is updated every iteration instead", RuntimeWarning)
+        return []
+    return bufs[:n]
+
+
+def _pcg_native(A, b, x0, tol, maxiter, x0_owned=False, skip_tail=False, defer_x=0):
     """pcg(A, damped_jacobi, b, x0, tol, maxiter) as one C call (``poms_pcg_jacobi``):
     the launches, device scalars and stop tests of :func:`_pcg_device`, bitwise the
     same iterates, without a Python round trip per launch."""
@@ -228,13 +272,17 @@ def _pcg_native(A, b, x0, tol, maxiter, x0_owned=False, skip_tail=False):
     opts = _lib.PcgOpts(float(tol), int(maxiter), 1e-6, 10, OMEGA,
                         -1 if d is None or d.prev is None else int(d.prev),
                         -1 if d is None or d.next is None else int(d.next), 1 if skip_tail else 0)
+    pbufs = _defer_buffers(A, V, int(defer_x)) if d is None else []
+    if pbufs:
+        pptrs = (C.c_void_p * len(pbufs))(*[w._data.data_ptr() for w in pbufs])
+        opts.n_pbuf, opts.pbuf = len(pbufs), pptrs
     info = _lib.PcgInfo()
     ptrs = (C.c_void_p * 5)(*[w._data.data_ptr() for w in work])
     _lib.call("poms_pcg_jacobi", A._h, d.native.h if d is not None else None,
               C.byref(opts), rt.ptr(b._data), rt.ptr(x._data), 0 if x0 is None else 1, ptrs, C.byref(info),
               rt.stream_handle())
     x._mark_written()
-    for w in work:
+    for w in work + pbufs:
         w._mark_written()
     A._calls += 1
     return x, {"niter": info.niter, "success": bool(info.success), "res_norm": info.res_norm}
