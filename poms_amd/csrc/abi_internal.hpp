@@ -21,8 +21,23 @@ struct poms_ctx {
 // region, kind bit 0 norm / bit 1 dot, into value index vi (+1 when both).
 struct SpecPart { int64_t off; int n; int kind; int vi; };
 
-// Created, configured and destroyed by abi_op.hip; the groups below say which file
-// writes what after creation.
+// Where one operator launch may write its per-block partials instead of the scratch
+// (op_run_epi's in/out argument): `dst` when all its sums fit in `cap` doubles, norms
+// first, dots behind them; on return `used` says whether they went there.
+struct PartRoute {
+    double* dst = nullptr;
+    int64_t cap = 0;
+    bool used = false;
+};
+
+// poms_pcg_jacobi's host-sum slots: defined in pcg_native.hip and incomplete everywhere
+// else, so no other file can touch the ring; poms_op_destroy frees them (null: nothing)
+namespace poms {
+struct PcgSlots;
+void pcg_slots_free(PcgSlots* s);
+}  // namespace poms
+
+// Created, configured and destroyed by abi_op.hip.
 struct poms_op {
     // ---- operator launch state (abi_op.hip; set at creation or by its setters) ----
     poms_ctx* ctx = nullptr;
@@ -56,44 +71,17 @@ struct poms_op {
     // by op_run_split only
     bool split_interior = false;
 
-    // ---- partials routing (read by abi_op.hip's op_run / op_run_j2) ----
-    // where a launch writes its per-block partials: norms at scratch + part_off, dots
-    // at scratch + (dot_base < 0 ? nblk : dot_base) + part_off (op_run_split puts two
-    // launches' partials side by side and reduces them once); written by op_run_split only
+    // ---- partials layout in the scratch (written by op_run_split only, restored on return) ----
+    // norms at scratch + part_off, dots at scratch + (dot_base < 0 ? nblk : dot_base) +
+    // part_off: op_run_split puts two launches' partials side by side and reduces them once
     int64_t part_off = 0, dot_base = -1;
-    // op_run: write the partials to part_dst instead of the scratch when they fit
-    // in part_cap doubles (last_part_host says whether they went there).  part_dst and
-    // part_cap are written by pcg_native.hip only, around one launch; last_part_host by
-    // op_run / op_run_j2
-    double* part_dst = nullptr;
-    int64_t part_cap = 0;
-    bool last_part_host = false;
     // blocks of the last launch's partials (op_run, stencil_run, poms_op_diag_scale;
     // pcg_native.hip's diag_scale_norm writes it too)
     int64_t last_partials = 0;
 
-    // ---- native pcg slots (pcg_native.hip only; freed by poms_op_destroy) ----
-    // native pcg loop (poms_pcg_jacobi): device scalars and the pinned host slots
-    double* sv_dev = nullptr;
-    double* sv_host = nullptr;
-    // poms_pcg_jacobi, one rank: ring of pinned host slots the reduction kernels
-    // write the host-read norms into.  sv_seq[i] = launch sequence number that armed
-    // slot i (-1: never); every launch numbered below sv_done is known complete (a
-    // value written by a later launch of the same stream has been read), so its slot
-    // can be re-armed without a stale write landing after the sentinel.
-    static constexpr int kSvRing = 48;
-    int sv_next = 0;
-    int64_t sv_seq_next = 0, sv_done = 0;
-    int64_t sv_seq[kSvRing];
-    // ... and per slot a region of kSvPart doubles the operator launch writes its
-    // per-block partial sums into (no reduction launch: the host adds them in the
-    // reduction kernel's order when it reads the slot).  sv_npart[i] = blocks of the
-    // launch that last used region i (0: none pending), sv_pkind[i] bit 0 norm
-    // partials at [0, n), bit 1 dot partials after them.
-    static constexpr int kSvPart = 4096;
-    double* sv_part = nullptr;   // kSvRing x kSvPart, pinned, device-mapped, armed unset
-    int sv_npart[kSvRing] = {};
-    int sv_pkind[kSvRing] = {};
+    // ---- native pcg loop (pcg_native.hip only; freed by poms_op_destroy) ----
+    double* sv_dev = nullptr;        // device scalars, then the deferred x pass's alphas
+    poms::PcgSlots* sv = nullptr;    // the pinned host-sum slots (pcg_slots_free)
     double* la_buf = nullptr;   // the two-sweep lookahead's fourth preconditioner buffer (zero ghosts)
     double* la_raw = nullptr;   // its allocation: la_buf sits la_off doubles in, on the work vectors' 128-B phase
     int64_t la_off = -1;
@@ -212,6 +200,9 @@ inline poms::RowGeom row_geom(const poms_layout* L) {
     return g;
 }
 
+// doubles of one of the operator's vectors, ghost planes included
+inline int64_t padded_len(const poms_op* o) { return (int64_t)(o->L.n[0] + 2 * o->L.pads[0]) * row_geom(&o->L).s0; }
+
 inline int upload(const double* host, size_t n, double** dev) {
     POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(dev), std::max<size_t>(n, 1) * sizeof(double)));
     if (n) POMS_HIP_CHECK(hipMemcpy(*dev, host, n * sizeof(double), hipMemcpyHostToDevice));
@@ -225,7 +216,8 @@ bool error_is_set();                         // a message is waiting in poms_las
 int ctx_device(const poms_ctx* ctx);         // for the sources that see poms_ctx opaque
 bool sweep2_ok(const poms_op* o);
 int op_run_epi(poms_op* op, int epilogue, double omega, const double* x, double* y, const double* b,
-               int64_t zb, int64_t ze, int64_t zb2, int64_t ze2, bool wn, bool wd, void* stream);
+               int64_t zb, int64_t ze, int64_t zb2, int64_t ze2, bool wn, bool wd, void* stream,
+               PartRoute* route = nullptr);
 int op_run_split(poms_op* op, int epilogue, double omega, const double* x, double* y, const double* b,
                  int64_t ib, int64_t ie, int64_t b1s, int64_t b1e, int64_t b2s, int64_t b2e, double* norm_out,
                  double* dot_out, const SplitHooks& h, void* stream);

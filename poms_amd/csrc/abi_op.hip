@@ -724,8 +724,9 @@ int poms_op_destroy(poms_op* o) {
     for (void* p : o->mf_tabs)
         if (p) (void)hipFree(p);
     if (o->mf_diag) (void)hipFree(o->mf_diag);
-    for (double* p : {o->sv_host, o->sv_part, o->spec_part, o->spec_host})
+    for (double* p : {o->spec_part, o->spec_host})
         if (p) (void)hipHostFree(p);
+    pcg_slots_free(o->sv);
     for (auto& g : o->spec_graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (o->cap_stream) (void)hipStreamDestroy(o->cap_stream);
@@ -940,7 +941,8 @@ static bool fused_dot_ok(const poms_op* o) {
 // General-stencil launch (FORM_STENCIL): the epilogues of op_run plus EPI_DIAG.
 static int stencil_run(poms_op* o, int epi, double omega, const double* x, double* y, const double* b,
                        int64_t zb, int64_t ze, int want_norm, void* stream, int want_dot, int64_t zb2,
-                       int64_t ze2) {
+                       int64_t ze2, PartRoute* route = nullptr) {
+    if (route) route->used = false;   // (its own partials layout: the scratch only)
     if (epi == EPI_JACOBI0) { set_error("general stencil: no two-sweeps-from-zero epilogue"); return 1; }
     if (want_dot && epi != EPI_JACOBI && epi != EPI_APPLYDOT) { set_error("general stencil: dot needs Jacobi / apply+dot"); return 1; }
     const RowGeom r = row_geom(&o->L);
@@ -967,7 +969,8 @@ static int stencil_run(poms_op* o, int epi, double omega, const double* x, doubl
 // allocated or synchronised here.
 static int matfree_run(poms_op* o, int epi, double omega, const double* x, double* y, const double* b,
                        int64_t zb, int64_t ze, int want_norm, void* stream, int want_dot, int64_t zb2,
-                       int64_t ze2) {
+                       int64_t ze2, PartRoute* route = nullptr) {
+    if (route) route->used = false;   // (stencil_run's layout: the scratch only)
     if (epi == EPI_JACOBI0) { set_error("matrix-free operator: no two-sweeps-from-zero epilogue"); return 1; }
     if (want_dot && epi != EPI_JACOBI && epi != EPI_APPLYDOT) { set_error("matrix-free operator: dot needs Jacobi / apply+dot"); return 1; }
     const RowGeom r = row_geom(&o->L);
@@ -1049,17 +1052,38 @@ static int resolve_variant(const poms_op* o, int epi) {
 bool poms::sweep2_ok(const poms_op* o) {
     if (o->ndim != 2 || o->pmax != 3 || general_form(o) || o->ghost_corners) return false;
     if (o->L.pads[1] != 3 || o->L.pads[2] != 3 || resolve_variant(o, EPI_JACOBI) != 9) return false;
-    const int64_t bytes = (int64_t)(o->L.n[0] + 2 * o->L.pads[0]) * row_geom(&o->L).s0 * 8;
-    return bytes < 0x7ffffff0LL;
+    return padded_len(o) * 8 < 0x7ffffff0LL;
 }
 
 extern "C" {
 
-// partials as op_run: norm (sweep k+1) and dot (sweep k) at part_dst / the scratch.
-// EPI_JACOBI3Z (x = b): all three sums or none, ||x1||^2, ||dr_2||^2, ||dr_3||^2 side by
-// side (part_dst, or scratch[0, 3n))
+// Where a launch of nblk blocks writes its partials (none wanted: null pointers): the
+// route's destination when its sums fit there (route->used), norms at *pn and dots behind
+// them at *pd; else the scratch, norms at part_off and dots at dot_base (default nblk) +
+// part_off.  The scratch must hold them even when the route takes them.  `three`
+// (EPI_JACOBI3Z): three sums side by side from *pn, which the scratch holds only in its
+// default layout and need not hold when the route takes them.
+static int part_place(poms_op* o, int64_t nblk, bool wn, bool wd, bool three, PartRoute* route, double** pn,
+                      double** pd) {
+    if (route) route->used = false;
+    *pn = *pd = nullptr;
+    if (!wn && !wd) return 0;
+    const int64_t dbase = o->dot_base < 0 ? nblk : o->dot_base;
+    const bool fits = three ? o->part_off == 0 && o->dot_base < 0 && 3 * nblk <= kScratch
+                            : o->part_off + nblk <= dbase && dbase + o->part_off + nblk <= kScratch;
+    const bool sink = route && route->dst && (three ? 3 : (wn ? 1 : 0) + (wd ? 1 : 0)) * nblk <= route->cap;
+    if (!fits && !(three && sink)) { set_error("too many blocks for the partial-sum scratch"); return 1; }
+    *pn = sink ? route->dst : o->ctx->scratch + o->part_off;
+    *pd = sink ? route->dst + (wn ? nblk : 0) : o->ctx->scratch + dbase + o->part_off;
+    if (sink) route->used = true;
+    return 0;
+}
+
+// partials as op_run: norm (sweep k+1) and dot (sweep k) at the route's destination / the
+// scratch.  EPI_JACOBI3Z (x = b): all three sums or none, ||x1||^2, ||dr_2||^2, ||dr_3||^2
+// side by side (the route's destination, or scratch[0, 3n))
 static int op_run_j2(poms_op* o, int epi, double omega, const double* x, double* y, const double* b, int want_norm,
-                     int want_dot, void* stream) {
+                     int want_dot, void* stream, PartRoute* route) {
     if (!sweep2_ok(o)) { set_error("two sweeps per launch: one-rank 2D p = 3 Kronecker operators (variant 9) only"); return 1; }
     if (x == y || b == y) { set_error("two sweeps per launch: x_out must not alias x_in or b"); return 1; }
     const bool fz = epi == EPI_JACOBI3Z;
@@ -1073,39 +1097,14 @@ static int op_run_j2(poms_op* o, int epi, double omega, const double* x, double*
     const int64_t nblk = (int64_t)g.tiles2 * g.tiles1;
     o->last_variant = 9;
     if (nblk == 0) { o->last_partials = 0; return 0; }
-    if (fz) {
-        double* s0 = nullptr;
-        o->last_part_host = false;
-        if (want_norm) {
-            if (o->part_dst && 3 * nblk <= o->part_cap) {
-                s0 = o->part_dst;
-                o->last_part_host = true;
-            } else if (o->part_off == 0 && o->dot_base < 0 && 3 * nblk <= kScratch) {
-                s0 = o->ctx->scratch;
-            } else {
-                set_error("too many blocks for the partial-sum scratch");
-                return 1;
-            }
-        }
-        KronPtrs p{b, y, b, o->a0t, o->b0t, o->a1, o->b1, o->a2, o->b2, s0 ? s0 + 2 * nblk : nullptr,
-                   s0 ? s0 + nblk : nullptr, nullptr};
-        if (kron2d_j2_launch(o->pmax, o->form, p, g, o->tc, omega, as_stream(stream), true, s0)) return 1;
+    double *pn = nullptr, *pd = nullptr;
+    if (part_place(o, nblk, want_norm, want_dot, fz, route, &pn, &pd)) return 1;
+    if (fz) {   // (pn: the three sums' base, pd = pn + nblk)
+        KronPtrs p{b, y, b, o->a0t, o->b0t, o->a1, o->b1, o->a2, o->b2, pn ? pn + 2 * nblk : nullptr, pd, nullptr};
+        if (kron2d_j2_launch(o->pmax, o->form, p, g, o->tc, omega, as_stream(stream), true, pn)) return 1;
         POMS_HIP_CHECK(hipGetLastError());
         o->last_partials = want_norm ? nblk : 0;
         return 0;
-    }
-    const int64_t dbase = o->dot_base < 0 ? nblk : o->dot_base;
-    if ((want_norm || want_dot) && (o->part_off + nblk > dbase || dbase + o->part_off + nblk > kScratch)) {
-        set_error("too many blocks for the partial-sum scratch");
-        return 1;
-    }
-    double* pn = o->ctx->scratch + o->part_off;
-    double* pd = o->ctx->scratch + dbase + o->part_off;
-    o->last_part_host = false;
-    if (o->part_dst && ((want_norm ? 1 : 0) + (want_dot ? 1 : 0)) * nblk <= o->part_cap) {
-        pn = o->part_dst;
-        pd = o->part_dst + (want_norm ? nblk : 0);
-        o->last_part_host = true;
     }
     KronPtrs p{x, y, b, o->a0t, o->b0t, o->a1, o->b1, o->a2, o->b2, want_norm ? pn : nullptr,
                want_dot ? pd : nullptr, nullptr};
@@ -1117,14 +1116,15 @@ static int op_run_j2(poms_op* o, int epi, double omega, const double* x, double*
 
 static int op_run(poms_op* o, int epi, double omega, const double* x, double* y, const double* b,
                   int64_t zb, int64_t ze, int want_norm, void* stream, int want_dot = 0,
-                  int64_t zb2 = 0, int64_t ze2 = 0) {
+                  int64_t zb2 = 0, int64_t ze2 = 0, PartRoute* route = nullptr) {
     if (!o || !x || !y) { set_error("null operator or vector"); return 1; }
     if (epi != EPI_APPLY && !b) { set_error("null right-hand side"); return 1; }
-    if (epi == EPI_JACOBI2 || epi == EPI_JACOBI3Z) return op_run_j2(o, epi, omega, x, y, b, want_norm, want_dot, stream);
+    if (epi == EPI_JACOBI2 || epi == EPI_JACOBI3Z)
+        return op_run_j2(o, epi, omega, x, y, b, want_norm, want_dot, stream, route);
     if (o->form == FORM_STENCIL)
-        return stencil_run(o, epi, omega, x, y, b, zb, ze, want_norm, stream, want_dot, zb2, ze2);
+        return stencil_run(o, epi, omega, x, y, b, zb, ze, want_norm, stream, want_dot, zb2, ze2, route);
     if (o->form == FORM_MATFREE)
-        return matfree_run(o, epi, omega, x, y, b, zb, ze, want_norm, stream, want_dot, zb2, ze2);
+        return matfree_run(o, epi, omega, x, y, b, zb, ze, want_norm, stream, want_dot, zb2, ze2, route);
     if (epi == EPI_APPLYDOT && !(o->variant == 4 || o->variant == 8 || o->variant == 9 || o->variant == 10)) {
         set_error("apply + x.y: kernel variants 4, 8, 9, 10 only");
         return 1;
@@ -1155,20 +1155,8 @@ static int op_run(poms_op* o, int epi, double omega, const double* x, double* y,
     if (op_geom(o, zb, ze, g, v, v5_to, zb2, ze2, epi)) return 1;
     const int64_t nblk = (int64_t)g.tiles2 * g.tiles1 * g.nchunks;
     if (nblk == 0) { o->last_partials = 0; return 0; }
-    const int64_t dbase = o->dot_base < 0 ? nblk : o->dot_base;
-    if ((want_norm || want_dot) &&
-        (o->part_off + nblk > dbase || dbase + o->part_off + nblk > kScratch)) {
-        set_error("too many blocks for the partial-sum scratch");
-        return 1;
-    }
-    double* pn = o->ctx->scratch + o->part_off;
-    double* pd = o->ctx->scratch + dbase + o->part_off;
-    o->last_part_host = false;
-    if (o->part_dst && ((want_norm ? 1 : 0) + (want_dot ? 1 : 0)) * nblk <= o->part_cap) {
-        pn = o->part_dst;
-        pd = o->part_dst + (want_norm ? nblk : 0);
-        o->last_part_host = true;
-    }
+    double *pn = nullptr, *pd = nullptr;
+    if (part_place(o, nblk, want_norm, want_dot, false, route, &pn, &pd)) return 1;
     KronPtrs p{x, y, b, o->a0t, o->b0t, o->a1, o->b1, o->a2, o->b2, want_norm ? pn : nullptr,
                want_dot ? pd : nullptr, o->rdiag0};
     poms_op::TimedLaunch* tlh = nullptr;
@@ -1260,7 +1248,7 @@ int poms_op_jacobi_from_zero(poms_op* op, double omega, const double* b, double*
 
 int poms_op_from_zero_supported(poms_op* op, int* yes) {
     if (!op || !yes) { set_error("poms_op_from_zero_supported: null argument"); return 1; }
-    const int64_t bytes = (int64_t)(op->L.n[0] + 2 * op->L.pads[0]) * row_geom(&op->L).s0 * 8;
+    const int64_t bytes = padded_len(op) * 8;
     // 2D (round 6, v3): not on a block of a decomposition (its ghost rows' x1 would need
     // the neighbours' diagonal)
     *yes = ((op->ndim == 3 || (op->ndim == 2 && !op->ghost_corners)) && !general_form(op) &&
@@ -1326,10 +1314,12 @@ int poms_op_set_ghost_corners(poms_op* op, int yes) {
 // may cover a second plane range [zb2, ze2) (the slab's other boundary).
 }  // extern "C"
 
-// One launch of `epilogue` over planes [zb, ze) + [zb2, ze2), its partials written
-// where op->part_off / dot_base say; the argument checks of poms_op_run_reduce2.
+// One launch of `epilogue` over planes [zb, ze) + [zb2, ze2), its partials written to
+// the route's destination where one is given and they fit, else where op->part_off /
+// dot_base say (part_place); the argument checks of poms_op_run_reduce2.
 int poms::op_run_epi(poms_op* op, int epilogue, double omega, const double* x, double* y, const double* b,
-                     int64_t zb, int64_t ze, int64_t zb2, int64_t ze2, bool wn, bool wd, void* stream) {
+                     int64_t zb, int64_t ze, int64_t zb2, int64_t ze2, bool wn, bool wd, void* stream,
+                     PartRoute* route) {
     switch (epilogue) {
         case EPI_APPLY:
             if (wn || wd) { set_error("poms_op_run_reduce: apply has no reductions"); return 1; }
@@ -1341,7 +1331,7 @@ int poms::op_run_epi(poms_op* op, int epilogue, double omega, const double* x, d
             break;
         case EPI_JACOBI:
             if (x == y) { set_error("jacobi sweep: x_out must not alias x_in"); return 1; }
-            if (op_run(op, EPI_JACOBI, omega, x, y, b, zb, ze, wn ? 1 : 0, stream, wd ? 1 : 0, zb2, ze2)) return 1;
+            if (op_run(op, EPI_JACOBI, omega, x, y, b, zb, ze, wn ? 1 : 0, stream, wd ? 1 : 0, zb2, ze2, route)) return 1;
             break;
         case EPI_JACOBI0:   // x = b: norm_out <- ||dr_2||^2, dot_out <- ||x1||^2
             {
@@ -1351,21 +1341,21 @@ int poms::op_run_epi(poms_op* op, int epilogue, double omega, const double* x, d
             }
             if (b == y) { set_error("jacobi from zero: x_out must not alias b"); return 1; }
             if (wn != wd) { set_error("jacobi from zero: both norms or neither"); return 1; }
-            if (op_run(op, EPI_JACOBI0, omega, b, y, b, zb, ze, wn ? 1 : 0, stream, wn ? 1 : 0, zb2, ze2)) return 1;
+            if (op_run(op, EPI_JACOBI0, omega, b, y, b, zb, ze, wn ? 1 : 0, stream, wn ? 1 : 0, zb2, ze2, route)) return 1;
             break;
         case EPI_JACOBI2:   // two sweeps from x: norm_out <- ||dr_{k+1}||^2, dot_out <- ||dr_k||^2
             if (zb != 0 || ze != 1 || zb2 != ze2) { set_error("two sweeps per launch: 2D (planes [0, 1))"); return 1; }
-            if (op_run(op, EPI_JACOBI2, omega, x, y, b, 0, 1, wn ? 1 : 0, stream, wd ? 1 : 0)) return 1;
+            if (op_run(op, EPI_JACOBI2, omega, x, y, b, 0, 1, wn ? 1 : 0, stream, wd ? 1 : 0, 0, 0, route)) return 1;
             break;
         case EPI_JACOBI3Z:   // sweeps 1-3 from x = 0 (x = b): norm_out <- ||dr_3||^2, dot_out <- ||dr_2||^2
             // (poms_op_run_reduce2 cannot return the third sum: poms_op_jacobi3_from_zero)
             if (zb != 0 || ze != 1 || zb2 != ze2) { set_error("three sweeps from zero: 2D (planes [0, 1))"); return 1; }
-            if (op_run(op, EPI_JACOBI3Z, omega, b, y, b, 0, 1, wn ? 1 : 0, stream, wd ? 1 : 0)) return 1;
+            if (op_run(op, EPI_JACOBI3Z, omega, b, y, b, 0, 1, wn ? 1 : 0, stream, wd ? 1 : 0, 0, 0, route)) return 1;
             break;
         case EPI_APPLYDOT:
             if (x == y) { set_error("apply: y must not alias x"); return 1; }
             if (wn || !wd) { set_error("apply + dot: dot_out only"); return 1; }
-            if (op_run(op, EPI_APPLYDOT, 0.0, x, y, x, zb, ze, 0, stream, 1, zb2, ze2)) return 1;
+            if (op_run(op, EPI_APPLYDOT, 0.0, x, y, x, zb, ze, 0, stream, 1, zb2, ze2, route)) return 1;
             break;
         default:
             set_error("poms_op_run_reduce: bad epilogue");

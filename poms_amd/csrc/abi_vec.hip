@@ -23,10 +23,10 @@ static int vec_common(poms_ctx* ctx, const poms_layout* L, int op, double a, dou
     // whole interior planes as one flat range (ghost rows / columns are zero in every
     // vector and stay zero -- unless the layout says they hold a neighbour's data);
     // the per-row kernel for fills, mixed alignments and ghost data
-    const int64_t off = (int64_t)g.pd0 * g.s0, count = (int64_t)g.n0 * g.s0;
-    auto at = [&](const double* v) { return v ? v + off : nullptr; };
+    const FlatRange fr = flat_range(g);
+    auto at = [&](const double* v) { return v ? v + fr.off : nullptr; };
     const bool flat = !(L->flags & POMS_LAYOUT_GHOST_DATA) &&
-                      vec_flat_launch(op, count, a, b, at(x), at(y), const_cast<double*>(at(z)),
+                      vec_flat_launch(op, fr.count, a, b, at(x), at(y), const_cast<double*>(at(z)),
                                       const_cast<double*>(at(w)), at(q), red ? ctx->scratch : nullptr,
                                       as_stream(stream), &nb, ab_dev) == 0;
     if (!flat && vec_launch(op, g, a, b, x, y, z, w, q, red ? ctx->scratch : nullptr, as_stream(stream), &nb,
@@ -58,12 +58,11 @@ int poms_vec_scale(poms_ctx* ctx, const poms_layout* L, double a, const double* 
 int poms::vec_copy_dot(poms_ctx* ctx, const poms_layout* L, const double* x, double* z, double* out_dev,
                        void* stream) {
     if (!ctx || !layout_ok(L) || !x || !z || !out_dev) { set_error("copy_dot: bad argument"); return 1; }
-    const RowGeom g = row_geom(L);
-    const int64_t off = (int64_t)g.pd0 * g.s0, count = (int64_t)g.n0 * g.s0;
+    const FlatRange fr = flat_range(row_geom(L));
     int nb = 0;
     static const bool cd_off = [] { const char* e = getenv("POMS_COPY_DOT"); return e && e[0] == '0'; }();
     if (!cd_off && !(L->flags & POMS_LAYOUT_GHOST_DATA) &&
-        vec_flat_launch(V_SCALEDOT, count, 1.0, 0.0, x + off, nullptr, z + off, nullptr, nullptr, ctx->scratch,
+        vec_flat_launch(V_SCALEDOT, fr.count, 1.0, 0.0, x + fr.off, nullptr, z + fr.off, nullptr, nullptr, ctx->scratch,
                         as_stream(stream), &nb) == 0) {
         reduce_wide_launch(ctx->scratch, nb, out_dev, as_stream(stream));
         POMS_HIP_CHECK(hipGetLastError());

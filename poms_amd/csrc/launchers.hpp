@@ -3,6 +3,8 @@
 #pragma once
 #include "common.hpp"
 
+#include <algorithm>
+#include <cstdint>
 #include <vector>
 
 namespace poms {
@@ -45,6 +47,17 @@ int vec_launch(int op, const RowGeom& g, double a, double b, const double* x, co
 int vec_flat_launch(int op, int64_t count, double a, double b, const double* x, const double* y,
                     double* z, double* w, const double* q, double* partial, hipStream_t st,
                     int* nblk_out, const double* ab = nullptr, const AlphaFold* af = nullptr);
+// The range the flat kernels run over: a padded vector's whole interior planes, `count`
+// doubles from `off` (ghost rows / columns inside it are zero in every vector).
+struct FlatRange { int64_t off, count; };
+inline FlatRange flat_range(const RowGeom& g) { return {(int64_t)g.pd0 * g.s0, (int64_t)g.n0 * g.s0}; }
+// vec_flat_launch's grid over `count` doubles at `p`, before its cap (POMS_VEC_BLOCKS): a
+// head double where p is off its 16-B phase, then 1024 pairs per block.  Callers that
+// size a partials region or a fold by the grid take it from here.
+inline int64_t vec_flat_blocks(int64_t count, const void* p) {
+    const int head = (reinterpret_cast<uintptr_t>(p) & 15) ? 1 : 0;
+    return std::max<int64_t>(1, ((count - head) / 2 + 256 * 4 - 1) / (256 * 4));
+}
 // x = fma(alpha[j], p_j, x) over `count` doubles for the n terms of `xa` (flat only; 1: the
 // pointers do not share their 16-B phase, nothing launched)
 int vec_xpass_launch(int64_t count, const XPassArgs& xa, const double* alpha, double* x, hipStream_t st);

@@ -16,6 +16,178 @@
 
 using namespace poms;
 
+// ---- the host-sum slots of poms_pcg_jacobi ------------------------------------
+namespace poms {
+
+// The sum of n per-block partials, added on the host in the order of
+// reduce_partials_kernel (256 strided running sums, the 64-lane xor butterfly, then
+// (w0 + w1) + (w2 + w3)): the same bits as the device reduction.
+static double host_reduce(const double* p, int n) {
+    double sv[256];
+    for (int t = 0; t < 256; ++t) {
+        double a = 0.0;
+        for (int i = t; i < n; i += 256) a += p[i];
+        sv[t] = a;
+    }
+    double red[4];
+    for (int w = 0; w < 4; ++w) {
+        double v[64], nv[64];
+        for (int l = 0; l < 64; ++l) v[l] = sv[64 * w + l];
+        for (int off = 32; off > 0; off >>= 1) {
+            for (int l = 0; l < 64; ++l) nv[l] = v[l] + v[l ^ off];
+            for (int l = 0; l < 64; ++l) v[l] = nv[l];
+        }
+        red[w] = v[0];
+    }
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// The sums `pk` (PcgSlots::pkind's bits) of a region of n blocks' partials into out:
+// [dot, norm], or the three sums of EPI_JACOBI3Z.
+static void reduce_region(const double* reg, int n, int pk, double* out) {
+    const bool wn = pk & 1, wd = pk & 2;
+    for (int i = 0; (pk & 4) && i < 3; ++i) out[i] = host_reduce(reg + (size_t)i * n, n);
+    if (pk & 4) return;
+    if (wn) out[wd ? 1 : 0] = host_reduce(reg, n);
+    if (wd) out[0] = host_reduce(reg + (wn ? n : 0), n);
+}
+
+// poms_pcg_jacobi, one rank: ring of pinned host slots the reduction kernels
+// write the host-read norms into.  seq[i] = launch sequence number that armed
+// slot i (-1: never); every launch numbered below `done` is known complete (a
+// value written by a later launch of the same stream has been read), so its slot
+// can be re-armed without a stale write landing after the sentinel.
+// ... and per slot a region of kSvPart doubles the operator launch writes its
+// per-block partial sums into (no reduction launch: the host adds them in the
+// reduction kernel's order when it reads the slot).  npart[i] = blocks of the
+// launch that last used region i (0: none pending), pkind[i] bit 0 norm
+// partials at [0, n), bit 1 dot partials after them, bit 2 three sums (EPI_JACOBI3Z).
+// (With a communicator only `host` is used, at fixed indices: PcgRun::hslot.)
+struct PcgSlots {
+    static constexpr int kSvRing = 48, kSvPart = 4096;
+    // an unwritten partial in a host region: a NaN payload no reduction produces
+    static constexpr uint64_t kPartUnset = 0x7ff8dead0000beefull;
+    double* host = nullptr;   // kSvRing sums, pinned, device-mapped
+    double* part = nullptr;   // kSvRing x kSvPart, pinned, device-mapped, armed unset
+    int next = 0;
+    int64_t seq_next = 0, done = 0;
+    int64_t seq[kSvRing];
+    int npart[kSvRing] = {}, pkind[kSvRing] = {};
+
+    int alloc() {
+        // coherent (fine-grained) and device-mapped: reduction kernels write the
+        // host-read norms straight into it
+        POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&host), kSvRing * sizeof(double),
+                                     hipHostMallocMapped | hipHostMallocCoherent));
+        POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&part), (size_t)kSvRing * kSvPart * sizeof(double),
+                                     hipHostMallocMapped | hipHostMallocCoherent));
+        part_arm(part, kSvRing * kSvPart);
+        for (int64_t& q : seq) q = -1;
+        return 0;
+    }
+    double* region(int h) { return part + (size_t)h * kSvPart; }
+    // the launch just queued wrote nblk blocks' partials of the sums `pk` into slot h's region
+    void pending(int h, int nblk, int pk) { npart[h] = nblk; pkind[h] = pk; }
+    static int64_t host_partials_max() {   // tuning: POMS_HOST_PARTIALS (0: always reduce on the device)
+        // read per launch (a getenv against a kernel launch): the parity tests switch it
+        // inside one process to run the device-reduction fall-back
+        const char* e = getenv("POMS_HOST_PARTIALS");
+        const int64_t m = e ? std::max<int64_t>(0, atoll(e)) : kSvPart / 2;
+        return std::min<int64_t>(m, kSvPart / 2);
+    }
+    // Arm `cnt` consecutive host slots for the next launch and return the first.
+    // Direct mode takes fresh slots from a ring: a launch the loop abandoned (an
+    // early damped-Jacobi stop leaves the next sweep queued) still writes ITS slot
+    // later, so a slot is re-armed only once that launch is known complete -- a value
+    // of a later launch has been read (launches of one stream finish in order) --
+    // else the stream is drained first (advisor finding, round 2).
+    int arm(int cnt, hipStream_t st) {
+        if (next + cnt > kSvRing) next = 0;
+        const int h = next;
+        next += cnt;
+        for (int i = 0; i < cnt; ++i)
+            if (seq[h + i] >= done) {
+                (void)hipStreamSynchronize(st);
+                done = seq_next;
+                break;
+            }
+        for (int i = 0; i < cnt; ++i) {
+            reinterpret_cast<volatile double*>(host)[h + i] = -1.0;   // norms are >= 0
+            seq[h + i] = seq_next;
+            if (npart[h + i] > 0) {   // an abandoned launch's partials (complete by now): re-arm
+                part_arm(region(h + i), pk_nsum(pkind[h + i]) * npart[h + i]);
+                pending(h + i, 0, 0);
+            }
+        }
+        ++seq_next;
+        return h;
+    }
+    // Spin while `unset()` holds; false: the stream has drained (or failed) and it still
+    // does -- never written, the launch failed.
+    template <class Unset>
+    static bool wait_written(Unset unset, hipStream_t st) {
+        for (long k = 1; unset(); ++k) {
+            __builtin_ia32_pause();
+            if ((k & 4095) == 0 && hipStreamQuery(st) != hipErrorNotReady) {
+                std::atomic_thread_fence(std::memory_order_seq_cst);
+                if (unset()) return false;
+            }
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+        return true;
+    }
+    // Wait for every partial of slot h's region and add them on the host (host_reduce)
+    // into the slot's sums; 1: one was never written.
+    int settle_partials(int h, hipStream_t st) {
+        const int n = npart[h];
+        double* reg = region(h);
+        const int nsum = pk_nsum(pkind[h]);
+        for (int i = 0; i < nsum * n; ++i)
+            if (!wait_written([&] { return part_unset(reg + i); }, st)) return 1;
+        reduce_region(reg, n, pkind[h], host + h);
+        part_arm(reg, nsum * n);
+        pending(h, 0, 0);
+        return 0;
+    }
+    // Sum i of the launch that armed slot h into *out: from its region's partials where
+    // it left them there, else the slot itself, spun on until the reduction kernel has
+    // replaced the sentinel.  1 (message set): the launch never wrote it.
+    int read(int h, int i, hipStream_t st, double* out) {
+        if (npart[h] > 0) {
+            if (settle_partials(h, st)) {
+                set_error("poms_pcg_jacobi: a launch did not write its partial sums");
+                return 1;
+            }
+            done = std::max(done, seq[h] + 1);
+            *out = host[h + i];
+            return 0;
+        }
+        const volatile double* v = reinterpret_cast<const volatile double*>(host) + h + i;
+        if (!wait_written([&] { return *v == -1.0; }, st)) {
+            set_error("poms_pcg_jacobi: a launch did not write its sum");
+            return 1;
+        }
+        done = std::max(done, seq[h + i] + 1);   // that launch and all before it are done
+        *out = *v;
+        return 0;
+    }
+    static int pk_nsum(int pk) { return (pk & 4) ? 3 : ((pk & 1) ? 1 : 0) + ((pk & 2) ? 1 : 0); }   // sums of kind pk
+    static bool part_unset(const double* v) { return *reinterpret_cast<const volatile uint64_t*>(v) == kPartUnset; }
+    static void part_arm(double* v, int n) {
+        volatile uint64_t* q = reinterpret_cast<volatile uint64_t*>(v);
+        for (int i = 0; i < n; ++i) q[i] = kPartUnset;
+    }
+};
+
+void pcg_slots_free(PcgSlots* s) {
+    if (!s) return;
+    for (double* p : {s->host, s->part})
+        if (p) (void)hipHostFree(p);
+    delete s;
+}
+
+}  // namespace poms
+
 // ---- native pcg + damped-Jacobi loop (poms_pcg_jacobi) ------------------------
 // The V-cycle's smoother (`sources/mg_jac.py:88,104` -> `sources/solvers.py:69-135`
 // with psolve = damped_jacobi, :167-235) as one C call: the same launches, device
@@ -27,8 +199,9 @@ namespace {
 // device scalars (the sums only the host reads live in host slots / comm ring slots)
 enum { SC_SR = 0, SC_PQ = 1, SC_ONE = 2, SC_ALPHA = 3, SC_ALPHA2 = 4, SC_BETA = 5, SC_SRN = 6, SC_N = 16 };
 enum { H_RR0 = 0, H_RR = 1, H_J0 = 2 /* 2 slots */, H_JN = 4 /* 2 slots */ };
-// an unwritten partial in a host region: a NaN payload no reduction produces
-constexpr uint64_t kPartUnset = 0x7ff8dead0000beefull;
+// a scalar folded into a flat launch: every block reads its partials, so only where
+// partials x blocks stays below this (2D; not the 3D grid)
+constexpr int64_t kFoldReadsMax = (int64_t)1 << 20;
 
 // (hist: where the deferred x pass reads this iteration's alpha, PcgRun::xflush; or null)
 __global__ void pcg_scalars_kernel(double* sc, int mode, double* hist) {
@@ -63,15 +236,15 @@ __global__ void __launch_bounds__(256) pcg_alpha_kernel(const double* __restrict
     if (hist != nullptr) hist[0] = a;
 }
 
-// s.r_new from the last damped-Jacobi sweep's per-block partials (reduce_partials_kernel's
-// order: the same bits), then beta = s.r_new / s.r_old and s.r_old <- s.r_new, in one
-// launch (one rank: saves the one-block reduction launch per pcg iteration)
 // s.r_old <- s.r_new, where a beta folded into the x/p update left it pending and no
 // folded r update follows (AlphaFold)
 __global__ void pcg_sr_fix_kernel(double* sc) {
     if (threadIdx.x == 0) sc[SC_SR] = sc[SC_SRN];
 }
 
+// s.r_new from the last damped-Jacobi sweep's per-block partials (reduce_partials_kernel's
+// order: the same bits), then beta = s.r_new / s.r_old and s.r_old <- s.r_new, in one
+// launch (one rank: saves the one-block reduction launch per pcg iteration)
 __global__ void __launch_bounds__(256) pcg_beta_kernel(const double* __restrict__ part, int count, double* sc) {
     __shared__ double red[4];
     double s = 0.0;
@@ -90,24 +263,41 @@ struct PcgRun {
     hipStream_t st;
     void* stv;
     double* sc;
-    double* host;
+    PcgSlots& sv;
     int64_t n0 = 1;
 
+    // The operator call of a communicator's rank.  h < 0: its sums reduced to the device
+    // (nrm, dot; null: not formed); else all-reduced into host slot h as [dot, norm].
+    int run_dist(int epi, const double* x, double* y, const double* b, bool wn, bool wd, double* nrm, double* dot,
+                 int h) {
+        const RowGeom g = row_geom(&op->L);
+        int tk0 = -1;
+        return poms_op_run_dist(op, comm, epi, o->omega, x, y, b, const_cast<double*>(x), g.s0, op->L.n[0],
+                                (int)op->L.pads[0], op->pmax, o->prev, o->next, 1, wn ? 1 : 0, wd ? 1 : 0, nrm, dot,
+                                h < 0 ? 0 : (wn ? 1 : 0) + (wd ? 1 : 0), h < 0 ? nullptr : sv.host + h,
+                                h < 0 ? &tk0 : &tk[h], stv);
+    }
     int run(int epi, const double* x, double* y, const double* b, double* nrm, double* dot) {
-        if (comm) {
-            const RowGeom g = row_geom(&op->L);
-            int tk = -1;
-            return poms_op_run_dist(op, comm, epi, o->omega, x, y, b, const_cast<double*>(x), g.s0, op->L.n[0],
-                                    (int)op->L.pads[0], op->pmax, o->prev, o->next, 1, nrm ? 1 : 0, dot ? 1 : 0, nrm,
-                                    dot, 0, nullptr, &tk, stv);
-        }
+        if (comm) return run_dist(epi, x, y, b, nrm, dot, nrm, dot, -1);
         return poms_op_run_reduce2(op, epi, o->omega, x, y, b, 0, n0, 0, 0, nrm, dot, 0, stv);
+    }
+    // alpha = s.r / p.q into the scalars (and hist_slot): p.q from the n partials at
+    // `part`, or with part null from sc[SC_PQ]
+    void launch_alpha(const double* part, int64_t n) {
+        if (part) hipLaunchKernelGGL(pcg_alpha_kernel, dim3(1), dim3(256), 0, st, part, (int)n, sc, hist_slot);
+        else hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, st, sc, 0, hist_slot);
+    }
+    // beta = s.r_new / s.r_old and s.r_old <- s.r_new: s.r_new from the last sweep's
+    // x . rhs partials (dot_part: reduced here), else from sc[SC_SRN]
+    void launch_beta(bool from_part) {
+        if (from_part) hipLaunchKernelGGL(pcg_beta_kernel, dim3(1), dim3(256), 0, st, dot_part, (int)dot_part_n, sc);
+        else hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, st, sc, 1, (double*)nullptr);
     }
     // q = A p, p.q and alpha: one rank folds p.q's reduction into the alpha kernel
     int apd_alpha(const double* p, double* q) {
-        if (comm || op->dot_base >= 0 || op->part_off != 0 || op->part_dst || general_form(op)) {
+        if (comm || general_form(op)) {
             if (run(EPI_APPLYDOT, p, q, p, nullptr, sc + SC_PQ) || allsum(sc + SC_PQ, 1)) return 1;
-            hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, st, sc, 0, hist_slot);
+            launch_alpha(nullptr, 0);
             POMS_HIP_CHECK(hipGetLastError());
             return 0;
         }
@@ -138,11 +328,8 @@ struct PcgRun {
     // pcg_beta_kernel and the plain update), -1 on error
     int xpupd_beta(double* x, double* p, const double* s) {
         if (!fold_on() || !direct() || (op->L.flags & POMS_LAYOUT_GHOST_DATA) || dot_part_n < 0) return 1;
-        const RowGeom g = row_geom(&op->L);
-        const int64_t off = (int64_t)g.pd0 * g.s0, count = (int64_t)g.n0 * g.s0;
-        const int head = (reinterpret_cast<uintptr_t>(x + off) & 15) ? 1 : 0;
-        const int64_t nbp = std::max<int64_t>(1, ((count - head) / 2 + 1023) / 1024);
-        if (dot_part_n * nbp > (int64_t)1 << 20) return 1;
+        const auto [off, count] = flat_range(row_geom(&op->L));
+        if (dot_part_n * vec_flat_blocks(count, x + off) > kFoldReadsMax) return 1;
         if (fix_sr()) return -1;   // (beta reads s.r_old at sc[SC_SR])
         AlphaFold bf;
         bf.part = dot_part;
@@ -160,7 +347,7 @@ struct PcgRun {
     int flush_alpha() {
         if (fix_sr()) return 1;
         if (!alpha_part) return 0;
-        hipLaunchKernelGGL(pcg_alpha_kernel, dim3(1), dim3(256), 0, st, alpha_part, (int)alpha_n, sc, hist_slot);
+        launch_alpha(alpha_part, alpha_n);
         alpha_part = nullptr;
         POMS_HIP_CHECK(hipGetLastError());
         return 0;
@@ -210,19 +397,15 @@ struct PcgRun {
     // pn = s + beta p (V_XPUPD's p, x untouched): beta folded where xpupd_beta folds it,
     // else from pcg_beta_kernel / pcg_scalars_kernel as the plain x/p update takes it
     int pupd(const double* s, const double* p, double* pn, bool part) {
-        const int head = (reinterpret_cast<uintptr_t>(pn + doff) & 15) ? 1 : 0;
-        const int64_t nbp = std::max<int64_t>(1, ((dcount - head) / 2 + 1023) / 1024);
-        const bool fold = part && fold_on() && dot_part_n * nbp <= (int64_t)1 << 20;
+        const bool fold = part && fold_on() && dot_part_n * vec_flat_blocks(dcount, pn + doff) <= kFoldReadsMax;
         if (fix_sr()) return 1;   // (beta reads s.r_old at sc[SC_SR])
         AlphaFold bf;
         if (fold) {
             bf.part = dot_part;
             bf.n = (int)dot_part_n;
             bf.sc = sc;
-        } else if (part) {
-            hipLaunchKernelGGL(pcg_beta_kernel, dim3(1), dim3(256), 0, st, dot_part, (int)dot_part_n, sc);
         } else {
-            hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, st, sc, 1, (double*)nullptr);
+            launch_beta(part);
         }
         int nb = 0;
         if (vec_flat_launch(V_PUPD, dcount, 0.0, 0.0, s + doff, p + doff, pn + doff, nullptr, nullptr, nullptr, st, &nb,
@@ -238,7 +421,7 @@ struct PcgRun {
     // blocks) for pcg_beta_kernel instead of reducing them itself (-1: it did not)
     const double* dot_part = nullptr;
     int64_t dot_part_n = -1;
-    int tk[poms_op::kSvRing] = {};   // with a communicator: the ring ticket of host slot h
+    int tk[PcgSlots::kSvRing] = {};   // with a communicator: the ring ticket of host slot h
     // a sum the device needs (alpha, beta): all-reduced, the compute stream waits
     int allsum(double* d, int cnt) { return comm ? poms_allreduce_sum(comm, d, cnt, stv, 1) : 0; }
     // A value only the host reads: one rank -- the reduction kernel writes it straight
@@ -250,196 +433,66 @@ struct PcgRun {
     // wait for that all-reduce and copy, ~40 us per sweep in profiles/r03/proxy/).
     bool direct() const { return comm == nullptr; }
     double* hslot(int h) {
-        if (direct()) return host + h;
+        if (direct()) return sv.host + h;
         double* d = nullptr;
         if (poms_comm_slot(comm, &d, &tk[h])) return nullptr;
         return d;
     }
-    int lazy_post(int h, int cnt) { return direct() ? 0 : poms_allreduce_to_host(comm, tk[h], cnt, host + h, stv); }
-    // an operator launch whose sums only the host reads: [dot, norm] from host slot h
-    int jrun(int epi, const double* x, double* y, const double* b, bool wn, bool wd, int h) {
-        if (direct()) {   // the launch writes its partials into slot h's host region
-            // (up to host_partials_max() blocks).  A/B on one box
-            // (profiles/r03/host_partials/): 2D 1027^2 cycle 4.5-5.2 -> 3.6-3.7 ms,
-            // 3D 515^3 195.0-195.5 -> 194.9-195.3 ms
-            op->part_dst = op->sv_part + (size_t)h * poms_op::kSvPart;
-            op->part_cap = ((wn ? 1 : 0) + (wd ? 1 : 0)) * host_partials_max();
-            const int rc = op_run_epi(op, epi, o->omega, x, y, b, 0, n0, 0, 0, wn, wd, stv);
-            op->part_dst = nullptr;
-            if (rc) return 1;
-            const int64_t n = op->last_partials;
-            if (op->last_part_host) {
-                op->sv_npart[h] = (int)n;
-                op->sv_pkind[h] = (wn ? 1 : 0) | (wd ? 2 : 0);
-                return 0;
-            }
-            // too many blocks for the region: reduce on the device into the slots
-            double* pdot = op->ctx->scratch + (op->dot_base < 0 ? n : op->dot_base);
-            if ((wn && reduce_launch(op->ctx->scratch, (int)n, host + h + (wd ? 1 : 0), st)) ||
-                (wd && reduce_launch(pdot, (int)n, host + h, st))) {
-                set_error("poms_pcg_jacobi: reduction launch failed");
-                return 1;
-            }
-            POMS_HIP_CHECK(hipGetLastError());
+    int lazy_post(int h, int cnt) { return direct() ? 0 : poms_allreduce_to_host(comm, tk[h], cnt, sv.host + h, stv); }
+    // The tail of a one-rank launch of n blocks that was offered a host region for its
+    // sums `pk` (PcgSlots::pkind's bits).  The partials went there (used): the region is
+    // recorded for the host -- slot h's, or with h < 0 the speculative one at scur, for
+    // value vi.  Else (too many blocks for the region) they are in the scratch, and
+    // reductions into d are queued: [dot, norm], or the three sums.
+    int sums_tail(int64_t n, int pk, bool used, int h, int vi, double* d) {
+        if (used) {
+            if (h >= 0) { sv.pending(h, (int)n, pk); return 0; }
+            sparts.push_back(SpecPart{scur, (int)n, pk, vi});
+            scur += PcgSlots::pk_nsum(pk) * n;
             return 0;
         }
-        const RowGeom g = row_geom(&op->L);
-        return poms_op_run_dist(op, comm, epi, o->omega, x, y, b, const_cast<double*>(x), g.s0, op->L.n[0],
-                                (int)op->L.pads[0], op->pmax, o->prev, o->next, 1, wn ? 1 : 0, wd ? 1 : 0, nullptr,
-                                nullptr, (wn ? 1 : 0) + (wd ? 1 : 0), host + h, &tk[h], stv);
-    }
-    // sweeps 1-3 from x = 0 (one rank): [||x1||^2, ||dr_2||^2, ||dr_3||^2] into slots h .. h+2
-    int jrun3(const double* rhs, double* y, int h) {
-        op->part_dst = op->sv_part + (size_t)h * poms_op::kSvPart;
-        op->part_cap = 3 * host_partials_max();
-        const int rc = op_run_epi(op, EPI_JACOBI3Z, o->omega, rhs, y, rhs, 0, n0, 0, 0, true, true, stv);
-        op->part_dst = nullptr;
-        if (rc) return 1;
-        const int64_t n = op->last_partials;
-        if (op->last_part_host) {
-            op->sv_npart[h] = (int)n;
-            op->sv_pkind[h] = 4;
-            return 0;
+        const double* scr = op->ctx->scratch;   // (norms, then dots: poms_op_run_reduce2's layout)
+        const bool wn = pk & 1, wd = pk & 2;
+        if ((pk & 4) ? (reduce_launch(scr, (int)n, d, st) || reduce_launch(scr + n, (int)n, d + 1, st) ||
+                        reduce_launch(scr + 2 * n, (int)n, d + 2, st))
+                     : ((wn && reduce_launch(scr, (int)n, d + (wd ? 1 : 0), st)) ||
+                        (wd && reduce_launch(scr + n, (int)n, d, st)))) {
+            set_error("poms_pcg_jacobi: reduction launch failed");
+            return 1;
         }
-        for (int i = 0; i < 3; ++i)
-            if (reduce_launch(op->ctx->scratch + i * n, (int)n, host + h + i, st)) {
-                set_error("poms_pcg_jacobi: reduction launch failed");
-                return 1;
-            }
         POMS_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    // Arm `cnt` consecutive host slots for the next launch and return the first.
-    // Direct mode takes fresh slots from a ring: a launch the loop abandoned (an
-    // early damped-Jacobi stop leaves the next sweep queued) still writes ITS slot
-    // later, so a slot is re-armed only once that launch is known complete -- a value
-    // of a later launch has been read (launches of one stream finish in order) --
-    // else the stream is drained first (advisor finding, round 2).
-    int arm(int fixed_h, int cnt) {
-        if (!direct()) return fixed_h;
-        if (op->sv_next + cnt > poms_op::kSvRing) op->sv_next = 0;
-        const int h = op->sv_next;
-        op->sv_next += cnt;
-        for (int i = 0; i < cnt; ++i)
-            if (op->sv_seq[h + i] >= op->sv_done) {
-                (void)hipStreamSynchronize(st);
-                op->sv_done = op->sv_seq_next;
-                break;
-            }
-        for (int i = 0; i < cnt; ++i) {
-            reinterpret_cast<volatile double*>(host)[h + i] = -1.0;   // norms are >= 0
-            op->sv_seq[h + i] = op->sv_seq_next;
-            if (op->sv_npart[h + i] > 0) {   // an abandoned launch's partials (complete by now): re-arm
-                part_arm(op->sv_part + (size_t)(h + i) * poms_op::kSvPart, pk_nsum(op->sv_pkind[h + i]) * op->sv_npart[h + i]);
-                op->sv_npart[h + i] = 0;
-                op->sv_pkind[h + i] = 0;
-            }
-        }
-        ++op->sv_seq_next;
-        return h;
+    // an operator launch whose sums only the host reads: [dot, norm] from host slot h
+    int jrun(int epi, const double* x, double* y, const double* b, bool wn, bool wd, int h) {
+        if (!direct()) return run_dist(epi, x, y, b, wn, wd, nullptr, nullptr, h);
+        // the launch writes its partials into slot h's host region (up to
+        // host_partials_max() blocks).  A/B on one box (profiles/r03/host_partials/):
+        // 2D 1027^2 cycle 4.5-5.2 -> 3.6-3.7 ms, 3D 515^3 195.0-195.5 -> 194.9-195.3 ms
+        PartRoute rt{sv.region(h), ((wn ? 1 : 0) + (wd ? 1 : 0)) * PcgSlots::host_partials_max()};
+        if (op_run_epi(op, epi, o->omega, x, y, b, 0, n0, 0, 0, wn, wd, stv, &rt)) return 1;
+        return sums_tail(op->last_partials, (wn ? 1 : 0) | (wd ? 2 : 0), rt.used, h, -1, sv.host + h);
     }
-    static int64_t host_partials_max() {   // tuning: POMS_HOST_PARTIALS (0: always reduce on the device)
-        // read per launch (a getenv against a kernel launch): the parity tests switch it
-        // inside one process to run the device-reduction fall-back
-        const char* e = getenv("POMS_HOST_PARTIALS");
-        const int64_t m = e ? std::max<int64_t>(0, atoll(e)) : poms_op::kSvPart / 2;
-        return std::min<int64_t>(m, poms_op::kSvPart / 2);
+    // sweeps 1-3 from x = 0 (one rank): [||x1||^2, ||dr_2||^2, ||dr_3||^2] into slots h .. h+2
+    int jrun3(const double* rhs, double* y, int h) {
+        PartRoute rt{sv.region(h), 3 * PcgSlots::host_partials_max()};
+        if (op_run_epi(op, EPI_JACOBI3Z, o->omega, rhs, y, rhs, 0, n0, 0, 0, true, true, stv, &rt)) return 1;
+        return sums_tail(op->last_partials, 4, rt.used, h, -1, sv.host + h);
     }
-    // Wait for every partial of slot h's region and add them on the host in the
-    // order of reduce_partials_kernel (256 strided running sums, the 64-lane xor
-    // butterfly, then (w0 + w1) + (w2 + w3)): the same bits as the device reduction.
-    static double host_reduce(const double* p, int n) {
-        double sv[256];
-        for (int t = 0; t < 256; ++t) {
-            double a = 0.0;
-            for (int i = t; i < n; i += 256) a += p[i];
-            sv[t] = a;
-        }
-        double red[4];
-        for (int w = 0; w < 4; ++w) {
-            double v[64], nv[64];
-            for (int l = 0; l < 64; ++l) v[l] = sv[64 * w + l];
-            for (int off = 32; off > 0; off >>= 1) {
-                for (int l = 0; l < 64; ++l) nv[l] = v[l] + v[l ^ off];
-                for (int l = 0; l < 64; ++l) v[l] = nv[l];
-            }
-            red[w] = v[0];
-        }
-        return (red[0] + red[1]) + (red[2] + red[3]);
-    }
-    int settle_partials(int h) {
-        const int n = op->sv_npart[h];
-        double* reg = op->sv_part + (size_t)h * poms_op::kSvPart;
-        const int nsum = pk_nsum(op->sv_pkind[h]);
-        for (int i = 0; i < nsum * n; ++i) {
-            for (long k = 1; part_unset(reg + i); ++k) {
-                __builtin_ia32_pause();
-                if ((k & 4095) == 0 && hipStreamQuery(st) != hipErrorNotReady) {
-                    std::atomic_thread_fence(std::memory_order_seq_cst);
-                    if (part_unset(reg + i)) return 1;   // never written: the launch failed
-                }
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        const bool wn = op->sv_pkind[h] & 1, wd = op->sv_pkind[h] & 2;
-        if (op->sv_pkind[h] & 4) {   // three sums, slots h .. h+2 (EPI_JACOBI3Z)
-            for (int i = 0; i < 3; ++i) host[h + i] = host_reduce(reg + (size_t)i * n, n);
-        } else {
-            if (wn) host[h + (wd ? 1 : 0)] = host_reduce(reg, n);
-            if (wd) host[h] = host_reduce(reg + (wn ? n : 0), n);
-        }
-        part_arm(reg, nsum * n);
-        op->sv_npart[h] = 0;
-        op->sv_pkind[h] = 0;
-        return 0;
-    }
-    // sums in a slot region: bit 0 a norm, bit 1 a dot, bit 2 three sums (EPI_JACOBI3Z)
-    static int pk_nsum(int pk) { return (pk & 4) ? 3 : ((pk & 1) ? 1 : 0) + ((pk & 2) ? 1 : 0); }
-    static bool part_unset(const double* v) {
-        uint64_t u;
-        const volatile uint64_t* q = reinterpret_cast<const volatile uint64_t*>(v);
-        u = *q;
-        return u == kPartUnset;
-    }
-    static void part_arm(double* v, int n) {
-        volatile uint64_t* q = reinterpret_cast<volatile uint64_t*>(v);
-        for (int i = 0; i < n; ++i) q[i] = kPartUnset;
-    }
+    // `cnt` host slots for the next launch: from the ring, or with a communicator the fixed ones
+    int arm(int fixed_h, int cnt) { return direct() ? sv.arm(cnt, st) : fixed_h; }
     // A failed wait (the shm sum timed out, a launch never wrote its sum) sets
     // `failed` and keeps poms_comm_wait's message: the loop returns 1 at its next
     // check instead of carrying a NaN into the stop tests (advisor, round 3).
     bool failed = false;
-    double fail() {
-        failed = true;
-        return std::nan("");
-    }
+    double fail() { failed = true; return std::nan(""); }
     double get(int h, int i = 0) {
         if (!direct()) {
             if (poms_comm_wait(comm, tk[h])) return fail();
-            return host[h + i];
+            return sv.host[h + i];
         }
-        if (op->sv_npart[h] > 0) {
-            if (settle_partials(h)) {
-                set_error("poms_pcg_jacobi: a launch did not write its partial sums");
-                return fail();
-            }
-            op->sv_done = std::max(op->sv_done, op->sv_seq[h] + 1);
-            return host[h + i];
-        }
-        const volatile double* v = reinterpret_cast<const volatile double*>(host) + h + i;
-        for (long n = 1; *v == -1.0; ++n) {
-            __builtin_ia32_pause();
-            if ((n & 4095) == 0 && hipStreamQuery(st) != hipErrorNotReady) {   // stream drained (or failed)
-                std::atomic_thread_fence(std::memory_order_seq_cst);
-                if (*v == -1.0) {   // never written: the launch failed
-                    set_error("poms_pcg_jacobi: a launch did not write its sum");
-                    return fail();
-                }
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        op->sv_done = std::max(op->sv_done, op->sv_seq[h + i] + 1);   // that launch and all before it are done
-        return *v;
+        double v = 0.0;
+        return sv.read(h, i, st, &v) ? fail() : v;
     }
     int dot(const double* a, const double* b, double* dst) {
         if (poms_vec_dot(op->ctx, &op->L, a, b, dst, stv)) return 1;
@@ -457,19 +510,17 @@ struct PcgRun {
     int rupd(double* r, const double* q, int h, double* x = nullptr, const double* p = nullptr,
              bool norm_only = false) {
         if (direct() && !(op->L.flags & POMS_LAYOUT_GHOST_DATA)) {
-            const RowGeom g = row_geom(&op->L);
-            const int64_t off = (int64_t)g.pd0 * g.s0, count = (int64_t)g.n0 * g.s0;
-            const int head = (reinterpret_cast<uintptr_t>(r + off) & 15) ? 1 : 0;
-            const int64_t nbp = std::max<int64_t>(1, ((count - head) / 2 + 1023) / 1024);   // (vec_flat_launch's grid, before its cap)
-            if (nbp <= host_partials_max()) {
+            const auto [off, count] = flat_range(row_geom(&op->L));
+            const int64_t nbp = vec_flat_blocks(count, r + off);
+            if (nbp <= PcgSlots::host_partials_max()) {
                 int nb = 0;
-                double* reg = op->sv_part + (size_t)h * poms_op::kSvPart;
+                double* reg = sv.region(h);
                 // alpha folded into this launch where its blocks' extra reads of the
                 // partials are small (2D: 468 partials x ~515 blocks; not the 3D grid's
                 // 495 x 65536): one launch less per pcg iteration (round 6)
                 AlphaFold af;
                 const bool fold = fold_on();
-                if (fold && alpha_part && alpha_n * nbp <= (int64_t)1 << 20) {
+                if (fold && alpha_part && alpha_n * nbp <= kFoldReadsMax) {
                     af.part = alpha_part;
                     af.n = (int)alpha_n;
                     af.sc = sc;
@@ -487,8 +538,7 @@ struct PcgRun {
                     if (af.part) sr_stale = false;
                     alpha_part = nullptr;
                     POMS_HIP_CHECK(hipGetLastError());
-                    op->sv_npart[h] = nb;
-                    op->sv_pkind[h] = 1;
+                    sv.pending(h, nb, 1);
                     return 0;
                 }
             }
@@ -516,16 +566,14 @@ struct PcgRun {
         if (direct() && !general_form(op)) {   // partials straight into slot h's host region
             const RowGeom g = row_geom(&op->L);
             const int nb = diag_scale_blocks(op->ndim == 3, g);
-            if (nb <= host_partials_max()) {
+            if (nb <= PcgSlots::host_partials_max()) {
                 int nl = 0;
                 diag_scale_launch(op->ndim == 3, op->form, g, op->pmax, (int)op->g0, o->omega, b, x, op->a0t,
-                                  op->b0t, op->a1, op->b1, op->dg2a, op->dg2b,
-                                  op->sv_part + (size_t)h * poms_op::kSvPart, st, &nl);
+                                  op->b0t, op->a1, op->b1, op->dg2a, op->dg2b, sv.region(h), st, &nl);
                 POMS_HIP_CHECK(hipGetLastError());
                 if (nl != nb) { set_error("diag scale: block count mismatch"); return 1; }
                 op->last_partials = nb;
-                op->sv_npart[h] = nb;
-                op->sv_pkind[h] = 1;
+                sv.pending(h, nb, 1);
                 return 0;
             }
         }
@@ -542,8 +590,7 @@ struct PcgRun {
     // drained.  If one of them fires, the call is repeated step by step (x0 restored).
     // The launches and their order are those of the step-by-step loop when no test
     // fires, so the result is the same bits (tests/test_gpu_solvers.py).
-    using SPart = SpecPart;
-    std::vector<SPart> sparts;
+    std::vector<SpecPart> sparts;
     int64_t scur = 0;       // next free double of op->spec_part
     int sn = 0;             // next free value index
     std::vector<int> schk;  // value indices tested against jtol^2 (< fires)
@@ -561,22 +608,9 @@ struct PcgRun {
         double* dn = wn ? op->spec_dev + vi + (wd ? 1 : 0) : nullptr;
         double* dd = wd ? op->spec_dev + vi : nullptr;
         if (!direct()) return run(epi, x, y, b, dn, dd);
-        op->part_dst = op->spec_part + scur;
-        op->part_cap = poms_op::kSpecPart - scur;
-        const int rc = op_run_epi(op, epi, o->omega, x, y, b, 0, n0, 0, 0, wn, wd, stv);
-        op->part_dst = nullptr;
-        if (rc) return 1;
-        const int64_t n = op->last_partials;
-        if (op->last_part_host) {
-            sparts.push_back(SPart{scur, (int)n, (wn ? 1 : 0) | (wd ? 2 : 0), vi});
-            scur += cnt * n;
-            return 0;
-        }
-        double* pdot = op->ctx->scratch + (op->dot_base < 0 ? n : op->dot_base);
-        if (wn) reduce_launch(op->ctx->scratch, (int)n, dn, st);
-        if (wd) reduce_launch(pdot, (int)n, dd, st);
-        POMS_HIP_CHECK(hipGetLastError());
-        return 0;
+        PartRoute rt{op->spec_part + scur, poms_op::kSpecPart - scur};
+        if (op_run_epi(op, epi, o->omega, x, y, b, 0, n0, 0, 0, wn, wd, stv, &rt)) return 1;
+        return sums_tail(op->last_partials, (wn ? 1 : 0) | (wd ? 2 : 0), rt.used, -1, vi, op->spec_dev + vi);
     }
     // damped_jacobi with every sweep queued (no stop test read); as damped_jacobi below
     int spec_damped_jacobi(const double* rhs, double* A, double* B, int dot_idx, double** out) {
@@ -629,9 +663,11 @@ struct PcgRun {
         static const bool j2_env = !(getenv("POMS_J2") && getenv("POMS_J2")[0] == '0');
         const bool j2 = j2_env && C && direct() && sweep2_ok(op);
         int cur = 0;                              // buffer of the latest queued x
-        struct Pend { int kind, h, buf, in; };    // 1: sweep norm in slot h; 2: the from-zero
-        Pend q[2];                                // pair; 3: a two-sweep launch from bufs[in];
-                                                  // 5: sweeps 1-3 from zero
+        // an open stop test: a sweep's norm in slot h; the from-zero pair; a two-sweep
+        // launch from bufs[in]; sweeps 1-3 from zero
+        enum PendKind { P_SWEEP, P_ZERO2, P_PAIR, P_ZERO3 };
+        struct Pend { PendKind kind; int h, buf, in; };
+        Pend q[2];
         int nq = 0, ring = 0, k0;
         int fz = 0;
         if (maxit >= 2 && maxit != 2 && !general_form(op)) (void)poms_op_from_zero_supported(op, &fz);
@@ -640,71 +676,53 @@ struct PcgRun {
         if (fz && j2 && j3_env && maxit >= 4) {   // [||x1||^2, ||dr2||^2, ||dr3||^2]
             const int h0 = arm(H_J0, 3);
             if (jrun3(rhs, A, h0)) return 1;
-            q[nq++] = Pend{5, h0, 0, -1};
+            q[nq++] = Pend{P_ZERO3, h0, 0, -1};
             k0 = 4;
         } else if (fz) {   // sweeps 1, 2 from x = 0 in one pass over rhs: [||x1||^2, ||dr2||^2]
             const int h0 = arm(H_J0, 2);
             if (jrun(EPI_JACOBI0, rhs, A, rhs, true, true, h0)) return 1;
-            q[nq++] = Pend{2, h0, 0, -1};
+            q[nq++] = Pend{P_ZERO2, h0, 0, -1};
             k0 = 3;
         } else {
             if (maxit < 1) { set_error("pcg: jacobi maxiter < 1"); return 1; }
             const int h = arm(H_JN, 1);
             if (diag_scale_norm(rhs, A, h)) return 1;
-            q[nq++] = Pend{1, h, 0, -1};
+            q[nq++] = Pend{P_SWEEP, h, 0, -1};
             ring = 1;
             k0 = 2;
         }
-        // the oldest open stop test: done with *res when it fires
-        auto settle = [&](bool& done, double*& res) {
-            done = false;
+        // The oldest open stop test.  S_DONE: it fired, *out is the result and the call
+        // returns 0; S_ERR: the call returns 1 (the values are damped_jacobi's returns).
+        enum Settled { S_OPEN = -1, S_DONE = 0, S_ERR = 1 };
+        auto settle = [&]() -> Settled {
             const Pend f = q[0];
             q[0] = q[1];
             --nq;
-            if (f.kind == 2) {
-                if (get(f.h, 0) < tol2) {   // the reference stops after sweep 1: x1 itself
-                    // (into the buffer the abandoned sweep 3 wrote; queued after every sweep
-                    // that reads it)
-                    double* x1 = bufs[(f.buf + 1) % nb];
-                    if (poms_op_diag_scale(op, o->omega, rhs, x1, 0, stv)) return 1;
-                    done = true;
-                    res = x1;
-                } else if (get(f.h, 1) < tol2) {
-                    done = true;
-                    res = bufs[f.buf];
-                }
-            } else if (f.kind == 5) {   // sweeps 1-3 from zero; x1 and x2 re-formed into the
-                double* xr = bufs[(f.buf + 1) % nb];   // buffer the abandoned next launch wrote
-                if (get(f.h, 0) < tol2) {
-                    if (poms_op_diag_scale(op, o->omega, rhs, xr, 0, stv)) return 1;
-                    done = true;
-                    res = xr;
-                } else if (get(f.h, 1) < tol2) {
-                    if (op_run_epi(op, EPI_JACOBI0, o->omega, rhs, xr, rhs, 0, n0, 0, 0, false, false, stv)) return 1;
-                    done = true;
-                    res = xr;
-                } else if (get(f.h, 2) < tol2) {
-                    done = true;
-                    res = bufs[f.buf];
-                }
-            } else if (f.kind == 3) {
-                if (get(f.h, 0) < tol2) {   // stopped after sweep k: x_k, one sweep from the
-                    // launch's input (intact: only one launch was queued after it) into the
-                    // buffer that launch wrote (abandoned)
-                    double* xk = bufs[(f.buf + 1) % nb];
-                    if (op_run_epi(op, EPI_JACOBI, o->omega, bufs[f.in], xk, rhs, 0, n0, 0, 0, false, false, stv))
-                        return 1;
-                    done = true;
-                    res = xk;
-                } else if (get(f.h, 1) < tol2) {
-                    done = true;
-                    res = bufs[f.buf];
-                }
-            } else if (get(f.h) < tol2) {
-                done = true;
+            double* res = nullptr;
+            // a stop before the launch's last sweep: that iterate is re-formed into the buffer
+            // the next launch wrote (abandoned; queued after every sweep that reads it)
+            double* xr = bufs[(f.buf + 1) % nb];
+            if (f.kind == P_SWEEP) {
+                if (get(f.h) < tol2) res = bufs[f.buf];
+            } else if (get(f.h, 0) < tol2) {
+                // after the launch's first sweep.  From zero: x1 itself, where the reference
+                // stops after sweep 1.  P_PAIR: x_k, one sweep from the launch's input
+                // (intact: only one launch was queued after it)
+                if (f.kind == P_PAIR
+                        ? op_run_epi(op, EPI_JACOBI, o->omega, bufs[f.in], xr, rhs, 0, n0, 0, 0, false, false, stv)
+                        : poms_op_diag_scale(op, o->omega, rhs, xr, 0, stv))
+                    return S_ERR;
+                res = xr;
+            } else if (f.kind == P_ZERO3 && get(f.h, 1) < tol2) {   // after sweep 2 of the three: x2
+                if (op_run_epi(op, EPI_JACOBI0, o->omega, rhs, xr, rhs, 0, n0, 0, 0, false, false, stv)) return S_ERR;
+                res = xr;
+            } else if (get(f.h, f.kind == P_ZERO3 ? 2 : 1) < tol2) {   // after its last sweep: the launch's output
                 res = bufs[f.buf];
             }
-            return failed ? 1 : 0;
+            if (failed) return S_ERR;
+            if (!res) return S_OPEN;
+            *out = res;
+            return S_DONE;
         };
         for (int k = k0; k <= maxit; ++k) {
             const bool last = k == maxit;
@@ -715,21 +733,16 @@ struct PcgRun {
                 if (jrun(EPI_JACOBI2, bufs[cur], bufs[nxt], rhs, true, true, h)) return 1;
                 // every open test is read now: a two-sweep launch's own (below) after the
                 // next launch, because the one after that would overwrite its input
-                while (nq > 0) {
-                    bool done;
-                    double* res = nullptr;
-                    if (settle(done, res)) return 1;
-                    if (done) { *out = res; return 0; }
-                }
-                q[nq++] = Pend{3, h, nxt, cur};
+                while (nq > 0)
+                    if (const Settled s = settle(); s != S_OPEN) return s;
+                q[nq++] = Pend{P_PAIR, h, nxt, cur};
                 cur = nxt;
                 ++k;
                 continue;
             }
             if (last) {   // the last sweep's norm cannot change the result: x . rhs instead
                 dot_part_n = -1;
-                if (direct() && dot_idx == SC_SRN && op->dot_base < 0 && op->part_off == 0 && !op->part_dst &&
-                    !general_form(op)) {   // its partials wait for pcg_beta_kernel
+                if (direct() && dot_idx == SC_SRN && !general_form(op)) {   // its partials wait for pcg_beta_kernel
                     if (op_run_epi(op, EPI_JACOBI, o->omega, bufs[cur], bufs[nxt], rhs, 0, n0, 0, 0, false, true, stv))
                         return 1;
                     dot_part_n = op->last_partials;
@@ -743,20 +756,13 @@ struct PcgRun {
                 ring ^= 1;
             }
             cur = nxt;
-            if (nq == depth || (nq > 0 && (q[0].kind == 3 || q[0].kind == 5))) {   // the test of the sweep `depth`
-                bool done;                                      // back, read after this one is queued
-                double* res = nullptr;
-                if (settle(done, res)) return 1;
-                if (done) { *out = res; return 0; }
-            }
-            if (!last) q[nq++] = Pend{1, h, cur, -1};
+            // the test of the sweep `depth` back, read after this one is queued
+            if (nq == depth || (nq > 0 && (q[0].kind == P_PAIR || q[0].kind == P_ZERO3)))
+                if (const Settled s = settle(); s != S_OPEN) return s;
+            if (!last) q[nq++] = Pend{P_SWEEP, h, cur, -1};
         }
-        while (nq > 0) {   // tests still open after the last sweep (its own has none)
-            bool done;
-            double* res = nullptr;
-            if (settle(done, res)) return 1;
-            if (done) { *out = res; return 0; }
-        }
+        while (nq > 0)   // tests still open after the last sweep (its own has none)
+            if (const Settled s = settle(); s != S_OPEN) return s;
         *dot_done = k0 <= maxit ? 1 : 0;
         *out = bufs[cur];
         return 0;
@@ -778,10 +784,8 @@ static int spec_issue(PcgRun& R, const double* b, double* x, int has_x0, double*
     void* stream = R.stv;
     double *r = work[0], *q = work[1];
     double* z[3] = {work[2], work[3], work[4]};
-    if (has_x0) {   // x0 is kept for the step-by-step repeat
-        const int64_t nbak = (int64_t)(op->L.n[0] + 2 * op->L.pads[0]) * row_geom(&op->L).s0;
-        POMS_HIP_CHECK(hipMemcpyAsync(op->spec_bak, x, nbak * sizeof(double), hipMemcpyDeviceToDevice, R.st));
-    }
+    if (has_x0)   // x0 is kept for the step-by-step repeat
+        POMS_HIP_CHECK(hipMemcpyAsync(op->spec_bak, x, padded_len(op) * sizeof(double), hipMemcpyDeviceToDevice, R.st));
     if (!has_x0) {
         if (poms_vec_fill(ctx, L, 0.0, x, stream)) return 1;
     } else if (R.run(EPI_RESID, x, r, b, nullptr, nullptr)) {
@@ -801,7 +805,7 @@ static int spec_issue(PcgRun& R, const double* b, double* x, int has_x0, double*
         if (c != p) (fa ? fb : fa) = c;
     for (int k = 1; k <= o->maxiter; ++k) {
         if (R.run(EPI_APPLYDOT, p, q, p, nullptr, R.sc + SC_PQ) || R.allsum(R.sc + SC_PQ, 1)) return 1;
-        hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 0, (double*)nullptr);
+        R.launch_alpha(nullptr, 0);   // (no deferred x pass here: hist_slot is null)
         const int vrr = R.svals(1);
         R.srr.push_back(vrr);
         if (o->skip_tail && k == o->maxiter) {   // the rest of this iteration is discarded
@@ -811,7 +815,7 @@ static int spec_issue(PcgRun& R, const double* b, double* x, int has_x0, double*
         if (poms_pcg_r_update_dev(ctx, L, R.sc + SC_ALPHA, r, q, op->spec_dev + vrr, stream)) return 1;
         double* sn = nullptr;
         if (R.spec_damped_jacobi(r, fa, fb, SC_SRN, &sn)) return 1;
-        hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 1, (double*)nullptr);
+        R.launch_beta(false);
         if (poms_pcg_xp_update_dev(ctx, L, R.sc + SC_ALPHA2, x, p, sn, stream)) return 1;
     }
     if (R.sn > poms_op::kSpecVals) { set_error("pcg speculative: too many values"); return 1; }
@@ -826,12 +830,7 @@ static int spec_finish(PcgRun& R, int vrr0, poms_pcg_info* info) {
     const poms_pcg_opts* o = R.o;
     POMS_HIP_CHECK(hipStreamSynchronize(R.st));
     std::vector<double> v(R.op->spec_host, R.op->spec_host + R.sn);
-    for (const PcgRun::SPart& s : R.sparts) {
-        const bool wn = s.kind & 1, wd = s.kind & 2;
-        const double* reg = R.op->spec_part + s.off;
-        if (wn) v[s.vi + (wd ? 1 : 0)] = PcgRun::host_reduce(reg, s.n);
-        if (wd) v[s.vi] = PcgRun::host_reduce(reg + (wn ? s.n : 0), s.n);
-    }
+    for (const SpecPart& s : R.sparts) reduce_region(R.op->spec_part + s.off, s.n, s.kind, v.data() + s.vi);
     const double tol2 = o->jtol * o->jtol;
     for (int i : R.schk)
         if (v[i] < tol2) return 2;
@@ -884,13 +883,13 @@ static int pcg_speculative(PcgRun& R, const double* b, double* x, int has_x0, do
     key[12] = (uint64_t)(op->timing ? 1 : 0) | ((uint64_t)(uint32_t)op->t_epi << 8) | ((uint64_t)(uint32_t)op->t_every << 32);
     key[13] = (uint64_t)(uintptr_t)R.comm | ((uint64_t)(uint32_t)(o->prev + 1) << 48) | ((uint64_t)(uint32_t)(o->next + 1) << 56);
     {   // whatever else changes the captured launches: the setters' generation, the tile
-        // geometry and ghost corners, the partials layout, and the env knobs read per launch
+        // geometry and ghost corners, and the env knobs read per launch (the scratch
+        // layout part_off / dot_base is always op_run_split's default here)
         const char* hp = getenv("POMS_HOST_PARTIALS");
         const char* la = getenv("POMS_PCG_LOOKAHEAD");
         key[14] = op->gen ^ ((uint64_t)(uint32_t)op->tout << 20) ^ ((uint64_t)(op->ghost_corners ? 1 : 0) << 52) ^
                   ((uint64_t)(uint32_t)(hp ? atoi(hp) + 1 : 0) << 40);
-        key[15] = (uint64_t)(uint32_t)(op->dot_base + 1) ^ ((uint64_t)(uint32_t)op->part_off << 32) ^
-                  ((uint64_t)(la && la[0] ? la[0] : 0) << 56);
+        key[15] = (uint64_t)(la && la[0] ? la[0] : 0) << 56;
     }
     poms_op::SpecGraph* hit = nullptr;
     for (auto& g : op->spec_graphs)
@@ -968,14 +967,63 @@ static bool pcg_spec_wanted(const poms_op*, const poms_pcg_opts* o) {
     return e && e[0] == '1' && o->maxiter >= 1 && o->jmaxiter >= 3;
 }
 
-static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o, const double* b, double* x,
-                           int has_x0, double* const* work, poms_pcg_info* info, void* stream);
+// ---- set-up: what a call needs allocated before its first launch ----
+// the device scalars (then the deferred x pass's alpha_hist[kXPassMax]) and the host-sum slots
+static int pcg_setup_slots(poms_op* op) {
+    if (!op->sv_dev) {
+        POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->sv_dev), (SC_N + kXPassMax) * sizeof(double)));
+        POMS_HIP_CHECK(hipMemset(op->sv_dev, 0, (SC_N + kXPassMax) * sizeof(double)));
+    }
+    if (!op->sv) {
+        PcgSlots* s = new PcgSlots;
+        if (s->alloc()) { pcg_slots_free(s); return 1; }
+        op->sv = s;
+    }
+    return 0;
+}
 
-// (a peer exchange that timed out during the call fails it: poms_comm_check)
-int poms_pcg_jacobi(poms_op* op, poms_comm* comm, const poms_pcg_opts* o, const double* b, double* x, int has_x0,
-                    double* const* work, poms_pcg_info* info, void* stream) {
-    if (pcg_jacobi_impl(op, comm, o, b, x, has_x0, work, info, stream)) return 1;
-    return comm ? poms_comm_check(comm) : 0;
+// speculative mode's value and partials buffers, and with an x0 its backup
+static int pcg_setup_spec(poms_op* op, int has_x0) {
+    if (!op->spec_dev) {
+        POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->spec_dev), poms_op::kSpecVals * sizeof(double)));
+        POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&op->spec_host), poms_op::kSpecVals * sizeof(double),
+                                     hipHostMallocDefault));
+        POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&op->spec_part), poms_op::kSpecPart * sizeof(double),
+                                     hipHostMallocMapped | hipHostMallocCoherent));
+    }
+    const int64_t nbak = padded_len(op);
+    if (has_x0 && op->spec_bak_n < nbak) {
+        if (op->spec_bak) POMS_HIP_CHECK(hipFree(op->spec_bak));
+        op->spec_bak = nullptr;
+        op->spec_bak_n = 0;
+        POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->spec_bak), nbak * sizeof(double)));
+        op->spec_bak_n = nbak;
+    }
+    return 0;
+}
+
+// The lookahead's fourth preconditioner buffer, op->la_buf.  It takes the work vectors'
+// 16-B / 128-B phase (they start `shift` doubles into their allocation on the
+// line-aligned layout; `like` is one of them): the flat vector kernels and v5's aligned
+// tiles then run on it exactly as on the other three buffers, with the same block split
+// of the sums (advisor, round 4).
+static int pcg_setup_lookahead(poms_op* op, const double* like, hipStream_t st) {
+    const int64_t nbuf = padded_len(op);
+    const int64_t off = (int64_t)((reinterpret_cast<uintptr_t>(like) & 127) / sizeof(double));
+    if (op->la_n < nbuf) {
+        if (op->la_raw) POMS_HIP_CHECK(hipFree(op->la_raw));
+        op->la_raw = op->la_buf = nullptr;
+        op->la_n = 0;
+        POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->la_raw), (nbuf + 16) * sizeof(double)));
+        op->la_n = nbuf;
+        op->la_off = -1;
+    }
+    if (op->la_off != off) {   // (re-)placed: zero ghosts
+        POMS_HIP_CHECK(hipMemsetAsync(op->la_raw, 0, (nbuf + 16) * sizeof(double), st));
+        op->la_off = off;
+        op->la_buf = op->la_raw + off;
+    }
+    return 0;
 }
 
 static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o, const double* b, double* x,
@@ -985,48 +1033,21 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
         if (!work[i]) { set_error("poms_pcg_jacobi: null work vector"); return 1; }
     if (o->maxiter < 0 || o->jmaxiter < 1) { set_error("poms_pcg_jacobi: bad iteration counts"); return 1; }
     POMS_HIP_CHECK(hipSetDevice(op->ctx->device));
-    if (!op->sv_dev) {
-        // (the scalars, then the deferred x pass's alpha_hist[kXPassMax])
-        POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->sv_dev), (SC_N + kXPassMax) * sizeof(double)));
-        POMS_HIP_CHECK(hipMemset(op->sv_dev, 0, (SC_N + kXPassMax) * sizeof(double)));
-        // coherent (fine-grained) and device-mapped: reduction kernels write the
-        // host-read norms straight into it
-        POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&op->sv_host), poms_op::kSvRing * sizeof(double),
-                                     hipHostMallocMapped | hipHostMallocCoherent));
-        POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&op->sv_part),
-                                     (size_t)poms_op::kSvRing * poms_op::kSvPart * sizeof(double),
-                                     hipHostMallocMapped | hipHostMallocCoherent));
-        PcgRun::part_arm(op->sv_part, poms_op::kSvRing * poms_op::kSvPart);
-        for (int64_t& q : op->sv_seq) q = -1;
-    }
+    if (pcg_setup_slots(op)) return 1;
+    const int64_t n0 = op->ndim == 3 ? op->L.n[0] : 1;
     if (pcg_spec_wanted(op, o)) {
-        const int64_t nbak = (int64_t)(op->L.n[0] + 2 * op->L.pads[0]) * row_geom(&op->L).s0;
-        if (!op->spec_dev) {
-            POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->spec_dev), poms_op::kSpecVals * sizeof(double)));
-            POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&op->spec_host), poms_op::kSpecVals * sizeof(double),
-                                         hipHostMallocDefault));
-            POMS_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&op->spec_part), poms_op::kSpecPart * sizeof(double),
-                                         hipHostMallocMapped | hipHostMallocCoherent));
-        }
-        if (has_x0 && op->spec_bak_n < nbak) {
-            if (op->spec_bak) POMS_HIP_CHECK(hipFree(op->spec_bak));
-            op->spec_bak = nullptr;
-            op->spec_bak_n = 0;
-            POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->spec_bak), nbak * sizeof(double)));
-            op->spec_bak_n = nbak;
-        }
-        PcgRun RS{op, comm, o, as_stream(stream), stream, op->sv_dev, op->sv_host};
-        RS.n0 = op->ndim == 3 ? op->L.n[0] : 1;
+        if (pcg_setup_spec(op, has_x0)) return 1;
+        PcgRun RS{op, comm, o, as_stream(stream), stream, op->sv_dev, *op->sv, n0};
         ++op->spec_calls;
         const int rc = pcg_speculative(RS, b, x, has_x0, work, info);
         if (rc != 2) return rc;
         ++op->spec_repeats;
         // a stop test fired: the step-by-step loop from the same inputs
         if (has_x0)
-            POMS_HIP_CHECK(hipMemcpyAsync(x, op->spec_bak, nbak * sizeof(double), hipMemcpyDeviceToDevice, as_stream(stream)));
+            POMS_HIP_CHECK(hipMemcpyAsync(x, op->spec_bak, padded_len(op) * sizeof(double), hipMemcpyDeviceToDevice,
+                                          as_stream(stream)));
     }
-    PcgRun R{op, comm, o, as_stream(stream), stream, op->sv_dev, op->sv_host};
-    R.n0 = op->ndim == 3 ? op->L.n[0] : 1;
+    PcgRun R{op, comm, o, as_stream(stream), stream, op->sv_dev, *op->sv, n0};
     poms_ctx* ctx = op->ctx;
     const poms_layout* L = &op->L;
     double *r = work[0], *q = work[1];
@@ -1037,9 +1058,9 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
     const int npb = std::min<int>(o->n_pbuf, kXPassMax - 1);   // (p_1 and npb more terms fill one x pass)
     if (npb >= 2 && o->pbuf && o->maxiter >= 1 && R.direct() && !(op->L.flags & POMS_LAYOUT_GHOST_DATA) &&
         !pcg_spec_wanted(op, o)) {
-        const RowGeom g = row_geom(&op->L);
-        R.doff = (int64_t)g.pd0 * g.s0;
-        R.dcount = (int64_t)g.n0 * g.s0;
+        const FlatRange fr = flat_range(row_geom(&op->L));
+        R.doff = fr.off;
+        R.dcount = fr.count;
         R.dx = x;
         const uintptr_t ph = reinterpret_cast<uintptr_t>(x) & 15;
         bool ok = R.dcount >= 4 && (ph & 7) == 0;
@@ -1070,46 +1091,20 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
     // 0 forces it on / off, default on for 2D operators, where the host's turn-around
     // per sweep is close to a sweep's GPU time): a fourth preconditioner buffer
     double* e4 = nullptr;
-    {
-        const char* le = getenv("POMS_PCG_LOOKAHEAD");
-        const bool la = R.direct() && (le && le[0] ? le[0] == '1' : op->ndim == 2);
-        if (la) {
-            // The buffer takes the work vectors' 16-B / 128-B phase (they start `shift`
-            // doubles into their allocation on the line-aligned layout): the flat vector
-            // kernels and v5's aligned tiles then run on it exactly as on the other three
-            // buffers, with the same block split of the sums (advisor, round 4).
-            const int64_t nbuf = (int64_t)(op->L.n[0] + 2 * op->L.pads[0]) * row_geom(&op->L).s0;
-            const int64_t off = (int64_t)((reinterpret_cast<uintptr_t>(work[2]) & 127) / sizeof(double));
-            if (op->la_n < nbuf) {
-                if (op->la_raw) POMS_HIP_CHECK(hipFree(op->la_raw));
-                op->la_raw = op->la_buf = nullptr;
-                op->la_n = 0;
-                POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->la_raw), (nbuf + 16) * sizeof(double)));
-                op->la_n = nbuf;
-                op->la_off = -1;
-            }
-            if (op->la_off != off) {   // (re-)placed: zero ghosts
-                POMS_HIP_CHECK(hipMemsetAsync(op->la_raw, 0, (nbuf + 16) * sizeof(double), R.st));
-                op->la_off = off;
-                op->la_buf = op->la_raw + off;
-            }
-            e4 = op->la_buf;
-        }
+    const char* le = getenv("POMS_PCG_LOOKAHEAD");
+    if (R.direct() && (le && le[0] ? le[0] == '1' : op->ndim == 2)) {
+        if (pcg_setup_lookahead(op, work[2], R.st)) return 1;
+        e4 = op->la_buf;
     }
     double* s = nullptr;
     int dd = 0;
     if (R.damped_jacobi(r, z[0], z[1], SC_SR, &s, &dd, e4)) return 1;
     if (!dd && R.dot(s, r, R.sc + SC_SR)) return 1;
     double* p = s;   // p keeps this buffer; later psolves use the others
-    double* fp[3] = {nullptr, nullptr, nullptr};
-    {
-        int nf = 0;
-        for (double* c : {z[0], z[1], z[2], e4})
-            if (c && c != p) fp[nf++] = c;
-    }
-    double* fa = fp[0];
-    double* fb = fp[1];
-    double* fc = fp[2];   // (nullptr without the lookahead)
+    double* fp[3] = {nullptr, nullptr, nullptr};   // (fp[2]: nullptr without the lookahead)
+    int nf = 0;
+    for (double* c : {z[0], z[1], z[2], e4})
+        if (c && c != p) fp[nf++] = c;
     int k = 0;
     int pring = 0;   // deferred: the p buffer p_{k+1} goes to
     double nrmr = nrmr0 * nrmr0;
@@ -1141,7 +1136,7 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
         }
         if (R.rupd(r, q, hrr)) return 1;
         double* sn = nullptr;
-        if (R.damped_jacobi(r, fa, fb, SC_SRN, &sn, &dd, fc)) return 1;   // queued before the read
+        if (R.damped_jacobi(r, fp[0], fp[1], SC_SRN, &sn, &dd, fp[2])) return 1;   // queued before the read
         if (!dd && R.dot(sn, r, R.sc + SC_SRN)) return 1;
         nrmr = R.get(hrr);
         if (R.failed) return 1;
@@ -1163,10 +1158,7 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
         if (fb < 0) return 1;
         if (fb > 0) {
             if (R.fix_sr()) return 1;
-            if (dd && R.dot_part_n >= 0)   // x . rhs's partials from the last sweep, reduced here
-                hipLaunchKernelGGL(pcg_beta_kernel, dim3(1), dim3(256), 0, R.st, R.dot_part, (int)R.dot_part_n, R.sc);
-            else
-                hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, R.st, R.sc, 1, (double*)nullptr);
+            R.launch_beta(dd && R.dot_part_n >= 0);
             if (poms_pcg_xp_update_dev(ctx, L, R.sc + SC_ALPHA2, x, p, sn, stream)) return 1;
         }
     }
@@ -1183,4 +1175,11 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
     info->res_norm = std::sqrt(nrmr);
     POMS_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+// (a peer exchange that timed out during the call fails it: poms_comm_check)
+int poms_pcg_jacobi(poms_op* op, poms_comm* comm, const poms_pcg_opts* o, const double* b, double* x, int has_x0,
+                    double* const* work, poms_pcg_info* info, void* stream) {
+    if (pcg_jacobi_impl(op, comm, o, b, x, has_x0, work, info, stream)) return 1;
+    return comm ? poms_comm_check(comm) : 0;
 }

@@ -531,25 +531,26 @@ int vec_flat_launch(int op, int64_t count, double a, double b, const double* x, 
                               : AlphaFold{};
     if (op == V_FILL || count < 4) return 1;
     int mis = -1;
+    const void* any = nullptr;   // (a pointer of the shared phase)
     for (const void* ptr : {(const void*)x, (const void*)y, (const void*)z, (const void*)w, (const void*)q}) {
         if (!ptr) continue;
         const int m = (int)(reinterpret_cast<uintptr_t>(ptr) & 15);
         if (m & 7) return 1;
         if (mis >= 0 && m != mis) return 1;
         mis = m;
+        any = ptr;
     }
     if (mis < 0) return 1;
     const int head = mis ? 1 : 0;
     const int64_t nd2 = (count - head) / 2;
     const int tail = (int)((count - head) - 2 * nd2);
-    int64_t nb = (nd2 + 256 * 4 - 1) / (256 * 4);
+    int64_t nb = vec_flat_blocks(count, any);
     static const int cap = [] {   // grid cap (tuning: POMS_VEC_BLOCKS, at most kMaxPartials)
         const char* e = getenv("POMS_VEC_BLOCKS");
         const int v = e ? atoi(e) : kMaxPartials;
         return v < 64 ? 64 : v > kMaxPartials ? kMaxPartials : v;
     }();
     if (nb > cap) nb = cap;
-    if (nb < 1) nb = 1;
     if (nblk_out) *nblk_out = (int)nb;
     static const bool plain = [] {
         const char* e = getenv("POMS_VEC_LOADS");
