@@ -134,19 +134,23 @@ def _coef_field(f, tabs, device):
     return torch.from_numpy(np.array(vals, dtype=np.float64, order="C")).to(device)
 
 
-def _device_field(f, tabs, device):
-    """A scalar field that is already a device tensor, used in place after the checks of
-    :func:`tensor_coef`."""
-    shape = tuple(t["nel"] * t["nq"] for t in tabs)
+def used_in_place(f: torch.Tensor, shape, device, what: str = "coefficient tensor") -> torch.Tensor:
+    """A device tensor an operator reads without a copy, after the checks: float64, of
+    ``shape``, on ``device``, contiguous."""
     if f.dtype != torch.float64:
-        raise TypeError(f"coefficient tensor must be float64, got {f.dtype}")
-    if tuple(f.shape) != shape:
-        raise ValueError(f"coefficient tensor has shape {tuple(f.shape)}, the quadrature grid {shape}")
+        raise TypeError(f"{what} must be float64, got {f.dtype}")
+    if tuple(f.shape) != tuple(shape):
+        raise ValueError(f"{what} has shape {tuple(f.shape)}, the quadrature grid {tuple(shape)}")
     if f.device != torch.device(device):
-        raise ValueError(f"coefficient tensor lives on {f.device}, the space on {device}")
+        raise ValueError(f"{what} lives on {f.device}, the space on {device}")
     if not f.is_contiguous():
-        raise ValueError("coefficient tensor must be contiguous (C order)")
+        raise ValueError(f"{what} must be contiguous (C order)")
     return f
+
+
+def _device_field(f, tabs, device):
+    """A scalar field that is already a device tensor, used in place."""
+    return used_in_place(f, tuple(t["nel"] * t["nq"] for t in tabs), device)
 
 
 def tensor_ncomp(ndim: int) -> int:
@@ -180,14 +184,33 @@ def tensor_coef(g, tabs, device):
         raise ValueError(f"tensor coefficient has {got[0]} components (shape {got}), a {len(tabs)}D operator "
                          f"needs ncomp = {ncomp}: the upper triangle in row-major order")
     if isinstance(g, torch.Tensor):
-        if g.dtype != torch.float64:
-            raise TypeError(f"tensor coefficient must be float64, got {g.dtype}")
-        if g.device != torch.device(device):
-            raise ValueError(f"tensor coefficient lives on {g.device}, the space on {device}")
-        if not g.is_contiguous():
-            raise ValueError("tensor coefficient must be contiguous (C order)")
-        return g
+        return used_in_place(g, want, device, "tensor coefficient")
     return torch.from_numpy(np.array(g, dtype=np.float64, order="C")).to(device)
+
+
+def quadrature_args(V: StencilVectorSpace, knots, nquad: int | None = None):
+    """``(tabs, args, keep)``: every axis's :func:`axis_tables`, checked against the space; the
+    constructors' arguments after the layout (``nel, nq, p, first, es, ee, basis, weights, nglob``,
+    three entries each, unused leading axes empty); the arrays the pointers refer to."""
+    nd = V.ndim
+    if len(knots) != nd:
+        raise ValueError(f"{nd}D space needs {nd} knot vectors")
+    tabs = [axis_tables(np.asarray(T, float), V.pads[d], nquad) for d, T in enumerate(knots)]
+    for d, t in enumerate(tabs):
+        if t["n"] != V.npts[d]:
+            raise ValueError(f"axis {d}: knots give {t['n']} basis functions, space has {V.npts[d]}")
+    lead, keep = 3 - nd, []
+
+    def pointers(key, dtype):
+        arrs = [np.ascontiguousarray(t[key], dtype=dtype) for t in tabs]
+        keep.extend(arrs)
+        return (C.c_void_p * 3)(*([None] * lead + [a.ctypes.data for a in arrs]))
+
+    ints = lambda key: (C.c_int * 3)(*([0] * lead + [int(t[key]) for t in tabs]))
+    nglob = (C.c_int64 * 3)(*([1] * lead + [int(t["n"]) for t in tabs]))
+    args = (ints("nel"), ints("nq"), ints("p"), pointers("first", np.int32), pointers("es", np.int32),
+            pointers("ee", np.int32), pointers("basis", np.float64), pointers("weights", np.float64), nglob)
+    return tabs, args, keep
 
 
 def assemble_stencil(V: StencilVectorSpace, knots, a=None, c=None, mass_coef: float = 1.0,
@@ -199,41 +222,18 @@ def assemble_stencil(V: StencilVectorSpace, knots, a=None, c=None, mass_coef: fl
     tensor coefficient: an array, a float64 device tensor, or a callable returning
     either, of shape ``(ncomp,) + quad_shape`` (see the module's text)."""
     nd = V.ndim
-    if len(knots) != nd:
-        raise ValueError(f"{nd}D space needs {nd} knot vectors")
-    tabs = [axis_tables(np.asarray(T, float), V.pads[d], nquad) for d, T in enumerate(knots)]
-    for d, t in enumerate(tabs):
-        if t["n"] != V.npts[d]:
-            raise ValueError(f"axis {d}: knots give {t['n']} basis functions, space has {V.npts[d]}")
-    lead = 3 - nd
-    keep = []
-
-    def arr3(key, ctype, np_dtype):
-        out = (C.c_void_p * 3)()
-        for k, t in enumerate(tabs):
-            a_ = np.ascontiguousarray(t[key], dtype=np_dtype)
-            keep.append(a_)
-            out[lead + k] = a_.ctypes.data
-        return out
-
-    ints = lambda key: [0] * lead + [int(t[key]) for t in tabs]
-    nel = (C.c_int * 3)(*ints("nel"))
-    nq = (C.c_int * 3)(*ints("nq"))
-    pp = (C.c_int * 3)(*ints("p"))
-    nglob = (C.c_int64 * 3)(*([1] * lead + [int(t["n"]) for t in tabs]))
+    tabs, tables, _keep = quadrature_args(V, knots, nquad)
     dev = f"cuda:{V.device}"
     avals, tensor = split_coef(a, tabs)
     aq = tensor_coef(avals, tabs, dev) if tensor else _coef_field(avals, tabs, dev)
     cq = _device_field(c, tabs, dev) if isinstance(c, torch.Tensor) and c.is_cuda else _coef_field(c, tabs, dev)
     h = C.c_void_p()
-    tables = (arr3("first", C.c_int, np.int32), arr3("es", C.c_int, np.int32), arr3("ee", C.c_int, np.int32),
-              arr3("basis", C.c_double, np.float64), arr3("weights", C.c_double, np.float64), nglob)
     tail = (None if cq is None else C.c_void_p(cq.data_ptr()), float(mass_coef),
             int(V.starts[0]) if nd == 3 else 0, C.byref(h))
     if tensor:
-        _lib.call("poms_op_assemble_stencil_tensor", V.ctx, nd, C.byref(V.layout), nel, nq, pp, *tables,
+        _lib.call("poms_op_assemble_stencil_tensor", V.ctx, nd, C.byref(V.layout), *tables,
                   C.c_void_p(aq.data_ptr()), tensor_ncomp(nd), *tail)
     else:
-        _lib.call("poms_op_assemble_stencil", V.ctx, nd, C.byref(V.layout), nel, nq, pp, *tables,
+        _lib.call("poms_op_assemble_stencil", V.ctx, nd, C.byref(V.layout), *tables,
                   None if aq is None else C.c_void_p(aq.data_ptr()), *tail)
     return StencilMatrix._from_handle(V, h)

@@ -79,6 +79,64 @@ static void toeplitz_range(const double* fa, const double* fb, int64_t n, int P,
     }
 }
 
+// A new general-form operator (FORM_STENCIL, FORM_MATFREE) on `layout`: its half-widths
+// are the layout's pads; the slab start g0 and the global axis-0 extent count in 3D only.
+static poms_op* new_general_op(poms_ctx* ctx, int ndim, int form, const poms_layout* layout, int64_t g0,
+                               int64_t n0_global) {
+    auto* o = new poms_op();
+    o->ctx = ctx;
+    o->ndim = ndim;
+    o->form = form;
+    o->L = *layout;
+    o->g0 = ndim == 3 ? g0 : 0;
+    o->n0g = ndim == 3 ? n0_global : 1;
+    for (int d = 0; d < 3; ++d) o->sp[d] = (int)layout->pads[d];
+    o->pmax = std::max(o->sp[0], std::max(o->sp[1], o->sp[2]));
+    return o;
+}
+
+// The axes a 1D / 2D operator does not use have n = 1 and no pads; else the error is set.
+static bool leading_axes_ok(const std::string& prefix, int ndim, const poms_layout* layout) {
+    for (int d = 0; d < 3 - ndim; ++d)
+        if (layout->n[d] != 1 || layout->pads[d] != 0) {
+            set_error(prefix + "unused leading axes need n = 1, pads = 0");
+            return false;
+        }
+    return true;
+}
+
+// The per-axis quadrature tables on the device as ax[3]; an unused leading axis gets one
+// element with one point of weight 1 and the constant function.  Every allocation goes
+// onto `owned`, which the caller frees, also after a failure (returns 1).
+static int upload_axes(int ndim, const int* nel, const int* nq, const int* p, const int* const* first,
+                       const int* const* es, const int* const* ee, const double* const* basis,
+                       const double* const* weights, const int64_t* nglob, AssembleAxis* ax,
+                       std::vector<void*>& owned) {
+    auto up = [&](const void* h, size_t bytes) -> void* {
+        void* d = nullptr;
+        if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
+        owned.push_back(d);
+        if (hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        return d;
+    };
+    static const int zero_i = 0;
+    static const double unit_b[2] = {1.0, 0.0}, unit_w = 1.0;
+    for (int d = 0; d < 3; ++d) {
+        const bool used = d >= 3 - ndim;
+        const int ne = used ? nel[d] : 1, q = used ? nq[d] : 1, pp = used ? p[d] : 0;
+        const int64_t n = used ? nglob[d] : 1;
+        AssembleAxis& A = ax[d];
+        A.first = static_cast<const int*>(up(used ? first[d] : &zero_i, ne * sizeof(int)));
+        A.es = static_cast<const int*>(up(used ? es[d] : &zero_i, n * sizeof(int)));
+        A.ee = static_cast<const int*>(up(used ? ee[d] : &zero_i, n * sizeof(int)));
+        A.basis = static_cast<const double*>(up(used ? basis[d] : unit_b, (size_t)ne * q * (pp + 1) * 2 * sizeof(double)));
+        A.w = static_cast<const double*>(up(used ? weights[d] : &unit_w, (size_t)ne * q * sizeof(double)));
+        A.nel = ne; A.nq = q; A.p = pp; A.n = (int)n;
+        if (!A.first || !A.es || !A.ee || !A.basis || !A.w) return 1;
+    }
+    return 0;
+}
+
 extern "C" {
 
 int poms_abi_version(void) { return POMS_ABI_VERSION; }
@@ -221,11 +279,7 @@ int poms_op_create_stencil(poms_ctx* ctx, int ndim, const poms_layout* layout, c
                            int64_t g0, int64_t n0_global, poms_op** op) {
     if (!ctx || !op || !data || !layout_ok(layout)) { set_error("poms_op_create_stencil: bad argument"); return 1; }
     if (ndim < 1 || ndim > 3) { set_error("poms_op_create_stencil: ndim 1..3"); return 1; }
-    for (int d = 0; d < 3 - ndim; ++d)
-        if (layout->n[d] != 1 || layout->pads[d] != 0) {
-            set_error("poms_op_create_stencil: unused leading axes need n = 1, pads = 0");
-            return 1;
-        }
+    if (!leading_axes_ok("poms_op_create_stencil: ", ndim, layout)) return 1;
     const RowGeom r = row_geom(layout);
     const int p[3] = {r.pd0, r.pd1, r.pd2};
     const int w[3] = {2 * p[0] + 1, 2 * p[1] + 1, 2 * p[2] + 1};
@@ -244,15 +298,7 @@ int poms_op_create_stencil(poms_ctx* ctx, int ndim, const poms_layout* layout, c
                 const double* src = data + row * W;
                 for (int64_t k = 0; k < W; ++k) soa[(size_t)(k * cst + lin)] = src[k];
             }
-    auto* o = new poms_op();
-    o->ctx = ctx;
-    o->ndim = ndim;
-    o->form = FORM_STENCIL;
-    o->pmax = std::max(p[0], std::max(p[1], p[2]));
-    o->L = *layout;
-    o->g0 = ndim == 3 ? g0 : 0;
-    o->n0g = ndim == 3 ? n0_global : 1;
-    for (int d = 0; d < 3; ++d) o->sp[d] = p[d];
+    poms_op* o = new_general_op(ctx, ndim, FORM_STENCIL, layout, g0, n0_global);
     if (upload(soa.data(), soa.size(), &o->coef)) { poms_op_destroy(o); return 1; }
     *op = o;
     return 0;
@@ -272,13 +318,8 @@ static int assemble_stencil_impl(const std::string& fn, poms_ctx* ctx, int ndim,
         return 1;
     }
     if (ndim < 1 || ndim > 3) { set_error(fn + ": ndim 1..3"); return 1; }
-    const int d0 = 3 - ndim;
-    for (int d = 0; d < d0; ++d)
-        if (layout->n[d] != 1 || layout->pads[d] != 0) {
-            set_error(fn + ": unused leading axes need n = 1, pads = 0");
-            return 1;
-        }
-    for (int d = d0; d < 3; ++d) {
+    if (!leading_axes_ok(fn + ": ", ndim, layout)) return 1;
+    for (int d = 3 - ndim; d < 3; ++d) {
         if (p[d] != layout->pads[d] || nel[d] < 1 || nq[d] < 1 || !first[d] || !es[d] || !ee[d] || !basis[d] ||
             !weights[d]) {
             set_error(fn + ": axis " + std::to_string(d) + " (degree must equal the pad)");
@@ -291,46 +332,10 @@ static int assemble_stencil_impl(const std::string& fn, poms_ctx* ctx, int ndim,
     const RowGeom r = row_geom(layout);
     const int64_t W = (int64_t)(2 * r.pd0 + 1) * (2 * r.pd1 + 1) * (2 * r.pd2 + 1);
     const int64_t cst = (int64_t)r.n0 * r.n1 * r.n2;
-    auto* o = new poms_op();
-    o->ctx = ctx;
-    o->ndim = ndim;
-    o->form = FORM_STENCIL;
-    o->pmax = std::max(r.pd0, std::max(r.pd1, r.pd2));
-    o->L = *layout;
-    o->g0 = ndim == 3 ? g0 : 0;
-    o->n0g = ndim == 3 ? nglob[0] : 1;
-    o->sp[0] = r.pd0; o->sp[1] = r.pd1; o->sp[2] = r.pd2;
+    poms_op* o = new_general_op(ctx, ndim, FORM_STENCIL, layout, g0, nglob[0]);
     std::vector<void*> tmp;
-    auto up_i = [&](const int* h, int64_t n) -> const int* {
-        void* d = nullptr;
-        if (hipMalloc(&d, std::max<int64_t>(n, 1) * sizeof(int)) != hipSuccess) return nullptr;
-        tmp.push_back(d);
-        if (hipMemcpy(d, h, n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return static_cast<const int*>(d);
-    };
-    auto up_d = [&](const double* h, int64_t n) -> const double* {
-        void* d = nullptr;
-        if (hipMalloc(&d, std::max<int64_t>(n, 1) * sizeof(double)) != hipSuccess) return nullptr;
-        tmp.push_back(d);
-        if (hipMemcpy(d, h, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return static_cast<const double*>(d);
-    };
-    static const int zero_i = 0;
-    static const double unit_b[2] = {1.0, 0.0}, unit_w = 1.0;
     AssembleAxis ax[3];
-    int rc = 0;
-    for (int d = 0; d < 3 && !rc; ++d) {
-        const bool used = d >= d0;
-        const int ne = used ? nel[d] : 1, q = used ? nq[d] : 1, pp = used ? p[d] : 0;
-        const int64_t n = used ? nglob[d] : 1;
-        ax[d].first = up_i(used ? first[d] : &zero_i, ne);
-        ax[d].es = up_i(used ? es[d] : &zero_i, n);
-        ax[d].ee = up_i(used ? ee[d] : &zero_i, n);
-        ax[d].basis = up_d(used ? basis[d] : unit_b, (int64_t)ne * q * (pp + 1) * 2);
-        ax[d].w = up_d(used ? weights[d] : &unit_w, (int64_t)ne * q);
-        ax[d].nel = ne; ax[d].nq = q; ax[d].p = pp; ax[d].n = (int)n;
-        if (!ax[d].first || !ax[d].es || !ax[d].ee || !ax[d].basis || !ax[d].w) rc = 1;
-    }
+    int rc = upload_axes(ndim, nel, nq, p, first, es, ee, basis, weights, nglob, ax, tmp);
     if (!rc && hipMalloc(reinterpret_cast<void**>(&o->coef), std::max<int64_t>(W * cst, 1) * sizeof(double)) != hipSuccess)
         rc = 1;
     if (!rc) {
@@ -372,11 +377,9 @@ static int create_matfree_impl(const std::string& name, poms_ctx* ctx, int ndim,
         set_error(fn + "distributed operators (slabs, Cart blocks) are not supported");
         return 1;
     }
-    const int d0 = 3 - ndim;
-    for (int d = 0; d < d0; ++d)
-        if (layout->n[d] != 1 || layout->pads[d] != 0) { set_error(fn + "unused leading axes need n = 1, pads = 0"); return 1; }
+    if (!leading_axes_ok(fn, ndim, layout)) return 1;
     const int T = matfree_tile();
-    for (int d = d0; d < 3; ++d) {
+    for (int d = 3 - ndim; d < 3; ++d) {
         const std::string ax = "axis " + std::to_string(d) + ": ";
         if (!first[d] || !es[d] || !ee[d] || !basis[d] || !weights[d]) { set_error(fn + ax + "null table"); return 1; }
         if (p[d] < 1 || p[d] > 3) { set_error(fn + ax + "degree must be 1..3"); return 1; }
@@ -419,42 +422,12 @@ static int create_matfree_impl(const std::string& name, poms_ctx* ctx, int ndim,
         if (!matfree_tensor_builds_ok(&why)) { set_error(fn + why); return 1; }
     }
     const RowGeom r = row_geom(layout);
-    auto* o = new poms_op();
-    o->ctx = ctx;
-    o->ndim = ndim;
-    o->form = FORM_MATFREE;
-    o->pmax = std::max(r.pd0, std::max(r.pd1, r.pd2));
-    o->L = *layout;
-    o->g0 = 0;
-    o->n0g = ndim == 3 ? nglob[0] : 1;
-    o->sp[0] = r.pd0; o->sp[1] = r.pd1; o->sp[2] = r.pd2;
+    poms_op* o = new_general_op(ctx, ndim, FORM_MATFREE, layout, 0, nglob[0]);
     o->mf_a = a_q;
     o->mf_tensor = tensor;
     o->mf_c = c_q;
     o->mf_mass = mass_coef;
-    auto up = [&](const void* h, size_t bytes) -> void* {
-        void* d = nullptr;
-        if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
-        o->mf_tabs.push_back(d);
-        if (hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return d;
-    };
-    static const int zero_i = 0;
-    static const double unit_b[2] = {1.0, 0.0}, unit_w = 1.0;
-    int rc = 0;
-    for (int d = 0; d < 3 && !rc; ++d) {
-        const bool used = d >= d0;
-        const int ne = used ? nel[d] : 1, q = used ? nq[d] : 1, pp = used ? p[d] : 0;
-        const int64_t n = used ? nglob[d] : 1;
-        AssembleAxis& A = o->mf_ax[d];
-        A.first = static_cast<const int*>(up(used ? first[d] : &zero_i, ne * sizeof(int)));
-        A.es = static_cast<const int*>(up(used ? es[d] : &zero_i, n * sizeof(int)));
-        A.ee = static_cast<const int*>(up(used ? ee[d] : &zero_i, n * sizeof(int)));
-        A.basis = static_cast<const double*>(up(used ? basis[d] : unit_b, (size_t)ne * q * (pp + 1) * 2 * sizeof(double)));
-        A.w = static_cast<const double*>(up(used ? weights[d] : &unit_w, (size_t)ne * q * sizeof(double)));
-        A.nel = ne; A.nq = q; A.p = pp; A.n = (int)n;
-        if (!A.first || !A.es || !A.ee || !A.basis || !A.w) rc = 1;
-    }
+    int rc = upload_axes(ndim, nel, nq, p, first, es, ee, basis, weights, nglob, o->mf_ax, o->mf_tabs);
     if (!rc && hipMalloc(reinterpret_cast<void**>(&o->mf_diag), std::max<int64_t>(ndof, 1) * sizeof(double)) != hipSuccess)
         rc = 1;
     if (!rc) {
@@ -654,15 +627,8 @@ int poms_op_galerkin_stencil(poms_op* fine, const poms_layout* coarse_layout, co
             }
     }
     POMS_HIP_CHECK(hipSetDevice(fine->ctx->device));
-    auto* o = new poms_op();
-    o->ctx = fine->ctx;
-    o->ndim = fine->ndim;
-    o->form = FORM_STENCIL;
-    o->pmax = fine->pmax;
-    o->L = *coarse_layout;
-    o->g0 = 0;
-    o->n0g = fine->ndim == 3 ? nc[0] : 1;
-    for (int d = 0; d < 3; ++d) o->sp[d] = fine->sp[d];
+    // (the coarse pads are the fine half-widths, checked above)
+    poms_op* o = new_general_op(fine->ctx, fine->ndim, FORM_STENCIL, coarse_layout, 0, nc[0]);
     std::vector<void*> tmp;
     auto dev = [&](const void* h, size_t bytes) -> void* {   // (h null: uninitialised)
         void* p = nullptr;

@@ -21,9 +21,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .assembly import _coef_field, assemble_stencil, axis_tables, split_coef, tensor_coef, tensor_ncomp
-from .mg import GalerkinVCycle, two_level_setup_1d
-from .splines import uniform_knots
+from .assembly import (_coef_field, assemble_stencil, axis_tables, quadrature_args, split_coef, tensor_coef,
+                       tensor_ncomp, used_in_place)
+from .mg import GalerkinVCycle, uniform_hierarchy
 from .stencil import KronOperator, StencilVectorSpace
 
 
@@ -35,15 +35,7 @@ def _coef_arg(f, tabs, device):
     if f is None:
         return None
     if isinstance(f, torch.Tensor):
-        if f.dtype != torch.float64:
-            raise TypeError(f"coefficient tensor must be float64, got {f.dtype}")
-        if tuple(f.shape) != shape:
-            raise ValueError(f"coefficient tensor has shape {tuple(f.shape)}, the quadrature grid {shape}")
-        if f.device != torch.device(device):
-            raise ValueError(f"coefficient tensor lives on {f.device}, the space on {device}")
-        if not f.is_contiguous():
-            raise ValueError("coefficient tensor must be contiguous (C order)")
-        return f
+        return used_in_place(f, shape, device)
     if not callable(f):
         got = np.shape(f)
         if got != () and got != shape:
@@ -94,17 +86,9 @@ class MatrixFreeOperator(KronOperator):
         nd = V.ndim
         if nd not in (2, 3):
             raise ValueError("matrix-free operators are 2D or 3D")
-        if len(knots) != nd:
-            raise ValueError(f"{nd}D space needs {nd} knot vectors")
-        tabs = [axis_tables(np.asarray(T, float), V.pads[d], nquad) for d, T in enumerate(knots)]
-        for d, t in enumerate(tabs):
-            if t["n"] != V.npts[d]:
-                raise ValueError(f"axis {d}: knots give {t['n']} basis functions, space has {V.npts[d]}")
-        self.space, self.form = V, "matfree"
-        self.pmax = max(max(V.pads), 1)
-        self.bands, self.timer, self._calls = {}, None, 0
+        tabs, tables, _keep = quadrature_args(V, knots, nquad)
+        self._init_base(V, "matfree")
         self._h = C.c_void_p()
-        self.pads, self.starts, self.ends = V.pads, V.starts, V.ends
         self.knots = [np.asarray(T, float).copy() for T in knots]
         self.nquad, self.mass_coef = nquad, float(mass_coef)
         self._args = (a, c)
@@ -113,29 +97,13 @@ class MatrixFreeOperator(KronOperator):
         # the arrays the handle borrows live as long as this object
         (self._aq, self.tensor), self._cq = _diffusion_arg(a, tabs, dev), _coef_arg(c, tabs, dev)
         self._diag = None
-        lead = 3 - nd
-        keep = []
-
-        def arr3(key, np_dtype):
-            out = (C.c_void_p * 3)()
-            for k, t in enumerate(tabs):
-                a_ = np.ascontiguousarray(t[key], dtype=np_dtype)
-                keep.append(a_)
-                out[lead + k] = a_.ctypes.data
-            return out
-
-        ints = lambda key: [0] * lead + [int(t[key]) for t in tabs]
-        nel, nq, pp = (C.c_int * 3)(*ints("nel")), (C.c_int * 3)(*ints("nq")), (C.c_int * 3)(*ints("p"))
-        nglob = (C.c_int64 * 3)(*([1] * lead + [int(t["n"]) for t in tabs]))
-        tables = (arr3("first", np.int32), arr3("es", np.int32), arr3("ee", np.int32),
-                  arr3("basis", np.float64), arr3("weights", np.float64), nglob)
         tail = (None if self._cq is None else C.c_void_p(self._cq.data_ptr()), self.mass_coef, C.byref(self._h))
         try:
             if self.tensor:
-                _lib.call("poms_op_create_matfree_tensor", V.ctx, nd, C.byref(V.layout), nel, nq, pp, *tables,
+                _lib.call("poms_op_create_matfree_tensor", V.ctx, nd, C.byref(V.layout), *tables,
                           C.c_void_p(self._aq.data_ptr()), tensor_ncomp(nd), *tail)
             else:
-                _lib.call("poms_op_create_matfree", V.ctx, nd, C.byref(V.layout), nel, nq, pp, *tables,
+                _lib.call("poms_op_create_matfree", V.ctx, nd, C.byref(V.layout), *tables,
                           None if self._aq is None else C.c_void_p(self._aq.data_ptr()), *tail)
         except _lib.PomsError as e:
             raise ValueError(str(e)) from None
@@ -191,8 +159,8 @@ class MatrixFreeVCycle(GalerkinVCycle):
     """:class:`~poms_amd.mg.GalerkinVCycle`'s cycle with a matrix-free finest level:
     ``ops[0]`` is a :class:`MatrixFreeOperator`, ``ops[1]`` the stencil assembled on
     level 1's knots, ``ops[l ≥ 2] = galerkin_stencil(ops[l-1], P[l-1])``, and the
-    coarsest level is inverted densely.  The sequence of a level is
-    ``GalerkinVCycle._level``, unchanged.
+    coarsest level is inverted densely.  The sequence of a level is the base's
+    ``_level``, unchanged.
 
     Level 1 is a *rediscretisation*, not a Galerkin product: it equals ``PᵀA₀P``
     exactly when ``a`` and ``c`` are integrated exactly on both levels (polynomials of
@@ -224,16 +192,7 @@ class MatrixFreeVCycle(GalerkinVCycle):
         for f in (a, c):
             if f is not None and not callable(f) and np.ndim(f) != 0:
                 raise ValueError("a / c must be None, scalars or callables here: they are sampled on two grids")
-        if ncells_fine < ncells_coarsest or ncells_coarsest < 1:
-            raise ValueError("need ncells_fine >= ncells_coarsest >= 1")
-        cells = [int(ncells_fine)]
-        while cells[-1] // 2 >= ncells_coarsest and cells[-1] % 2 == 0:
-            cells.append(cells[-1] // 2)
-        if len(cells) < 2:
-            raise ValueError("the hierarchy needs at least two levels (even cell counts)")
-        knots = [uniform_knots(p, N) for N in cells]
-        P1 = [two_level_setup_1d(p, knots[l], knots[l + 1])[2] for l in range(len(cells) - 1)]
-        V = StencilVectorSpace([len(knots[0]) - p - 1] * ndim, [p] * ndim, device=device, align=True)
+        cells, knots, P1, V = uniform_hierarchy(p, ncells_fine, ncells_coarsest, ndim, device)
         a1, c1 = a, c
         if mapping is not None:
             pull = lambda T: mapping.pullback([axis_tables(T, p, nquad)["points"].reshape(-1)] * ndim, a=a, c=c,

@@ -40,8 +40,9 @@ import torch
 from . import _lib
 from . import runtime as rt
 from .multilevels import KronTransfer, knots_to_insert
-from .solvers import damped_jacobi, defer_x_count, pcg
-from .splines import assemble_1d, matrix_multi_stages, uniform_knots
+from .solvers import damped_jacobi, defer_x_count, pcg, pcg_kron
+from .splines import (array_to_mat_stencil, assemble_1d, band_to_dense, collocation_cardinal_splines,
+                      matrix_multi_stages, uniform_knots)
 from .stencil import F64, KronOperator, StencilVector, StencilVectorSpace
 
 
@@ -69,61 +70,70 @@ def galerkin_coarse_dense(Mc: np.ndarray, Kc: np.ndarray, ndim: int, mass_coef: 
     return A
 
 
-class TwoLevelVCycle:
-    """Two-level V-cycle on an ``ndim``-D tensor B-spline space of degree ``p``."""
+def dyadic_cells(ncells_fine: int, ncells_coarsest: int) -> list:
+    """Cells per axis of every level: ``ncells_fine`` halved while it is even and the
+    half is not below ``ncells_coarsest``."""
+    if ncells_fine < ncells_coarsest or ncells_coarsest < 1:
+        raise ValueError("need ncells_fine >= ncells_coarsest >= 1")
+    cells = [int(ncells_fine)]
+    while cells[-1] % 2 == 0 and (half := cells[-1] // 2) >= ncells_coarsest:
+        cells.append(half)
+    if len(cells) < 2:
+        raise ValueError("the hierarchy needs at least two levels (even cell counts)")
+    return cells
 
-    def __init__(self, p: int, ncells_fine: int, ncells_coarse: int = 8, ndim: int = 3, *,
-                 dist=None, mass_coef: float = 1.0, device=None, knots_fine=None, knots_coarse=None,
-                 tol: float = 1e-6, maxiter: int = 10, chunk: int = 0, align: bool = True,
-                 post_smoother: str = "jacobi", fused_restrict: bool | None = None):
-        self.p, self.ndim = int(p), int(ndim)
-        if post_smoother not in ("jacobi", "glt"):
-            raise ValueError("post_smoother must be 'jacobi' (mg_jac.py) or 'glt' (mg_glt.py)")
-        self.post_smoother = post_smoother
-        Tc = uniform_knots(p, ncells_coarse) if knots_coarse is None else np.asarray(knots_coarse, float)
-        Tf = uniform_knots(p, ncells_fine) if knots_fine is None else np.asarray(knots_fine, float)
-        T, Ts, P1 = two_level_setup_1d(p, Tf, Tc)
-        self.Tc, self.Tf, self.T, self.Ts, self.P1 = Tc, Tf, T, Ts, P1
-        n = len(T) - p - 1
-        self.n = n
-        M, K = assemble_1d(T, p)
-        self.M1d, self.K1d = M, K
-        # line-aligned rows (pitch a multiple of 16 doubles): the v5 operator kernel
-        # then stores whole 128-B lines only (DESIGN.md §3)
-        self.space = StencilVectorSpace([n] * ndim, [p] * ndim, dist=dist, device=device, align=align)
-        self.A = KronOperator.laplace(self.space, [M] * ndim, [K] * ndim, mass_coef=mass_coef)
-        if chunk:
-            self.A.set_chunk(chunk)
-        self.transfer = KronTransfer(self.space, [P1] * ndim)
-        # residual -> restriction in one pass over x and b (KronTransfer.resid_restrict);
-        # False: the residual vector and the restriction, as the reference computes them.
-        # None: fused in 3D (515^3: 0.70 ms against 0.92 for the pair), not in 2D, where
-        # the passes are latency-bound (1027^2: 44.8 against 42.5 us; DESIGN.md §3.10)
-        if fused_restrict is None:   # (POMS_FUSED_RESTRICT: 0 never, all in every dimension)
-            fr = os.environ.get("POMS_FUSED_RESTRICT", "1")
-            fused_restrict = fr == "all" or (ndim == 3 and fr != "0")
-        self.fused_restrict = bool(fused_restrict) and self.transfer.set_operator(self.A)
-        from .splines import band_to_dense
-        Md, Kd = band_to_dense(M), band_to_dense(K)
-        Mc, Kc = P1.T @ Md @ P1, P1.T @ Kd @ P1
-        Ac = galerkin_coarse_dense(Mc, Kc, ndim, mass_coef)
+
+def uniform_hierarchy(p: int, ncells_fine: int, ncells_coarsest: int, ndim: int, device=None):
+    """``(cells, knots, P1, V)`` of the dyadic uniform hierarchy: the cells and knots of
+    every level, the 1D prolongations between them, and the finest level's space."""
+    cells = dyadic_cells(ncells_fine, ncells_coarsest)
+    knots = [uniform_knots(p, N) for N in cells]
+    P1 = [two_level_setup_1d(p, knots[l], knots[l + 1])[2] for l in range(len(cells) - 1)]
+    V = StencilVectorSpace([len(knots[0]) - p - 1] * ndim, [p] * ndim, device=device, align=True)
+    return cells, knots, P1, V
+
+
+def _smoother_counts(maxiters, nlevels: int) -> list:
+    out = [10] * (nlevels - 1) if maxiters is None else [int(m) for m in maxiters]
+    if len(out) != nlevels - 1:
+        raise ValueError(f"maxiters needs {nlevels - 1} entries")
+    return out
+
+
+class _VCycle:
+    """What the V-cycles share: the sequence of one level, the right-hand side of ones and
+    the dense solve on the coarsest level.  A constructor sets ``tol`` and, per level with
+    a coarser one below it, ``ops``, ``spaces``, ``transfers``, ``fused`` (residual ->
+    restriction in one pass) and ``maxiters``, then calls :meth:`_set_coarse`."""
+
+    glt = None   # level 0's post-smoother factors where it is pcg_kron (TwoLevelVCycle)
+
+    def _set_coarse(self, Ac: np.ndarray) -> None:
+        """The coarsest level from its dense operator: the inverse (the reference's
+        ``splu``) applied on the device, and the coarse vectors of every level."""
         self.Ac = Ac
-        lu = sla.lu_factor(Ac)
-        Ainv = sla.lu_solve(lu, np.eye(Ac.shape[0]))
+        Ainv = sla.lu_solve(sla.lu_factor(Ac), np.eye(Ac.shape[0]))
         dev = f"cuda:{self.space.device}"
         self.Ainv = torch.from_numpy(np.ascontiguousarray(Ainv)).to(dev)
-        self.rc = torch.empty(Ac.shape[0], dtype=F64, device=dev)
+        self.rcs = [torch.empty(tr.ncoarse, dtype=F64, device=dev) for tr in self.transfers]
         self.xc = torch.empty(Ac.shape[0], dtype=F64, device=dev)
-        self.tol, self.maxiter = tol, maxiter
-        self.glt = None
-        if post_smoother == "glt":
-            from .splines import array_to_mat_stencil, collocation_cardinal_splines
-            Cm = array_to_mat_stencil(n, p, collocation_cardinal_splines(p, n))
-            self.glt = [Cm] * ndim
+        self.infos = [None] * len(self.transfers)
+
+    @property
+    def nlevels(self) -> int:
+        return len(self.transfers) + 1
 
     @property
     def ndof(self) -> int:
         return self.space.dimension
+
+    @property
+    def space(self) -> StencilVectorSpace:
+        return self.spaces[0]
+
+    @property
+    def A(self) -> KronOperator:
+        return self.ops[0]
 
     def rhs_ones(self) -> StencilVector:
         """``bf[i] = 1`` on every owned coefficient (`sources/mg_jac.py:57-62`)."""
@@ -139,33 +149,98 @@ class TwoLevelVCycle:
                   rt.ptr(out), rt.stream_handle())
         return out
 
-    def cycle(self, bf: StencilVector, x0: StencilVector | None = None):
-        """One V-cycle; returns ``(xf2, info_pre, info_pos)``."""
-        A = self.A
+    def _level(self, l: int, b: StencilVector, x0: StencilVector | None) -> StencilVector:
+        A, tr, n = self.ops[l], self.transfers[l], self.maxiters[l]
         # (_skip_tail: a smoother call's last iteration ends at x and r.r, see solvers.pcg)
         # (_defer_x: x brought up to date once per call where that pays, see solvers.defer_x_count)
-        dx = defer_x_count(A, self.space, self.maxiter)
-        xf, info_pre = pcg(A, damped_jacobi, bf, x0=x0, tol=self.tol, maxiter=self.maxiter, _skip_tail=True,
-                           _defer_x=dx)
-        if self.fused_restrict:
-            rc = self.transfer.resid_restrict(A, bf, xf, out=self.rc)
+        dx = defer_x_count(A, self.spaces[l], n)
+        x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=n, _skip_tail=True, _defer_x=dx)
+        if self.fused[l]:
+            rc = tr.resid_restrict(A, b, x, out=self.rcs[l])
         else:
-            rf = A.residual(bf, xf)
-            rc = self.transfer.restrict(rf, out=self.rc)
-        xc = self.coarse_solve(rc, self.xc)
-        self.transfer.prolong_add(xc, xf)
-        xf.update_ghost_regions()
-        if self.glt is not None:
-            from .solvers import pcg_kron
-            xf2, info_pos = pcg_kron(A, self.glt, bf, x0=xf, tol=self.tol, maxiter=self.p + 1, _skip_tail=True)
+            rc = tr.restrict(A.residual(b, x), out=self.rcs[l])
+        if l + 1 == len(self.transfers):
+            ec = self.coarse_solve(rc, self.xc)
         else:
-            # (xf is this cycle's own temporary: iterate in its buffer, no copy)
-            xf2, info_pos = pcg(A, damped_jacobi, bf, x0=xf, tol=self.tol, maxiter=self.maxiter, _x0_owned=True,
-                                _skip_tail=True, _defer_x=dx)
-        return xf2, info_pre, info_pos
+            Vc = self.spaces[l + 1]
+            bc = Vc.empty()
+            Vc.interior(bc._data).copy_(rc.view(Vc.local_npts))
+            bc._mark_written()
+            bc.update_ghost_regions()
+            ecv = self._level(l + 1, bc, None)
+            ec = Vc.interior(ecv._data).contiguous().view(-1)
+        tr.prolong_add(ec, x)
+        x.update_ghost_regions()
+        if l == 0 and self.glt is not None:
+            x, ipos = pcg_kron(A, self.glt, b, x0=x, tol=self.tol, maxiter=self.p + 1, _skip_tail=True)
+        else:
+            # (x is this cycle's own temporary, never the caller's x0: iterate in its buffer, no copy)
+            x, ipos = pcg(A, damped_jacobi, b, x0=x, tol=self.tol, maxiter=n, _x0_owned=True, _skip_tail=True,
+                          _defer_x=dx)
+        if self.infos[l] is None:
+            self.infos[l] = (ipre, ipos)
+        return x
+
+    def cycle(self, b: StencilVector, x0: StencilVector | None = None):
+        """One V-cycle from level 0; returns ``(x, infos)``, ``infos[l] = (info_pre,
+        info_post)`` of level l's first visit in this cycle."""
+        self.infos = [None] * len(self.transfers)
+        x = self._level(0, b, x0)
+        return x, list(self.infos)
 
 
-class MultilevelVCycle:
+class TwoLevelVCycle(_VCycle):
+    """Two-level V-cycle on an ``ndim``-D tensor B-spline space of degree ``p``."""
+
+    def __init__(self, p: int, ncells_fine: int, ncells_coarse: int = 8, ndim: int = 3, *,
+                 dist=None, mass_coef: float = 1.0, device=None, knots_fine=None, knots_coarse=None,
+                 tol: float = 1e-6, maxiter: int = 10, chunk: int = 0, align: bool = True,
+                 post_smoother: str = "jacobi", fused_restrict: bool | None = None):
+        self.p, self.ndim = int(p), int(ndim)
+        if post_smoother not in ("jacobi", "glt"):
+            raise ValueError("post_smoother must be 'jacobi' (mg_jac.py) or 'glt' (mg_glt.py)")
+        self.post_smoother = post_smoother
+        Tc = uniform_knots(p, ncells_coarse) if knots_coarse is None else np.asarray(knots_coarse, float)
+        Tf = uniform_knots(p, ncells_fine) if knots_fine is None else np.asarray(knots_fine, float)
+        T, Ts, P1 = two_level_setup_1d(p, Tf, Tc)
+        self.Tc, self.Tf, self.T, self.Ts, self.P1 = Tc, Tf, T, Ts, P1
+        self.n = n = len(T) - p - 1
+        self.M1d, self.K1d = M, K = assemble_1d(T, p)
+        # line-aligned rows (pitch a multiple of 16 doubles): the v5 operator kernel
+        # then stores whole 128-B lines only (DESIGN.md §3)
+        V = StencilVectorSpace([n] * ndim, [p] * ndim, dist=dist, device=device, align=align)
+        A = KronOperator.laplace(V, [M] * ndim, [K] * ndim, mass_coef=mass_coef)
+        if chunk:
+            A.set_chunk(chunk)
+        self.spaces, self.ops, self.transfers = [V], [A], [KronTransfer(V, [P1] * ndim)]
+        # residual -> restriction in one pass over x and b (KronTransfer.resid_restrict);
+        # False: the residual vector and the restriction, as the reference computes them.
+        # None: fused in 3D (515^3: 0.70 ms against 0.92 for the pair), not in 2D, where
+        # the passes are latency-bound (1027^2: 44.8 against 42.5 us; DESIGN.md §3.10)
+        if fused_restrict is None:   # (POMS_FUSED_RESTRICT: 0 never, all in every dimension)
+            fr = os.environ.get("POMS_FUSED_RESTRICT", "1")
+            fused_restrict = fr == "all" or (ndim == 3 and fr != "0")
+        self.fused = [bool(fused_restrict) and self.transfer.set_operator(A)]
+        Md, Kd = band_to_dense(M), band_to_dense(K)
+        self._set_coarse(galerkin_coarse_dense(P1.T @ Md @ P1, P1.T @ Kd @ P1, ndim, mass_coef))
+        self.tol, self.maxiters = tol, [maxiter]
+        if post_smoother == "glt":
+            Cm = array_to_mat_stencil(n, p, collocation_cardinal_splines(p, n))
+            self.glt = [Cm] * ndim
+
+    # the one level's entries of the base's lists, under the names of `sources/mg_jac.py`
+    transfer = property(lambda self: self.transfers[0])
+    rc = property(lambda self: self.rcs[0])
+    maxiter = property(lambda self: self.maxiters[0], lambda self, m: self.maxiters.__setitem__(0, m))
+    fused_restrict = property(lambda self: self.fused[0], lambda self, f: self.fused.__setitem__(0, bool(f)))
+
+    def cycle(self, bf: StencilVector, x0: StencilVector | None = None):
+        """One V-cycle; returns ``(xf2, info_pre, info_pos)``."""
+        self.infos = [None]
+        return (self._level(0, bf, x0),) + self.infos[0]
+
+
+class MultilevelVCycle(_VCycle):
     """V-cycle over a hierarchy of nested uniform B-spline spaces (SURVEY §8f
     rank 1: the reference's two-level cycle `sources/mg_jac.py:84-119` applied
     recursively, with every level's operator, smoothing and transfers on the
@@ -186,36 +261,18 @@ class MultilevelVCycle:
     def __init__(self, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *,
                  dist=None, mass_coef: float = 1.0, device=None, tol: float = 1e-6, maxiters=None,
                  align: bool = True, chunk: int = 0, fused_restrict: bool | None = None):
-        if ncells_fine < ncells_coarsest or ncells_coarsest < 1:
-            raise ValueError("need ncells_fine >= ncells_coarsest >= 1")
+        self.cells = cells = dyadic_cells(ncells_fine, ncells_coarsest)
         self.p, self.ndim, self.tol = int(p), int(ndim), tol
-        cells = [int(ncells_fine)]
-        while cells[-1] // 2 >= ncells_coarsest and cells[-1] % 2 == 0:
-            cells.append(cells[-1] // 2)
-        if len(cells) < 2:
-            raise ValueError("the hierarchy needs at least two levels (even cell counts)")
-        self.cells = cells
-        self.nlevels = L = len(cells)
-        self.maxiters = [10] * (L - 1) if maxiters is None else [int(m) for m in maxiters]
-        if len(self.maxiters) != L - 1:
-            raise ValueError(f"maxiters needs {L - 1} entries")
-        knots = [uniform_knots(p, N) for N in cells]
-        self.knots = knots
-        self.P1 = []
-        self.M1d, self.K1d, self.spaces, self.ops, self.transfers = [], [], [], [], []
-        for l in range(L):
-            n = len(knots[l]) - p - 1
-            M, K = assemble_1d(knots[l], p)
-            self.M1d.append(M)
-            self.K1d.append(K)
-            if l < L - 1:
-                _, _, P1 = two_level_setup_1d(p, knots[l], knots[l + 1])
-                self.P1.append(P1)
-            if l == L - 1:
-                break
-            V = StencilVectorSpace([n] * ndim, [p] * ndim, dist=dist if l == 0 else None, device=device,
-                                   align=align)
-            A = KronOperator.laplace(V, [M] * ndim, [K] * ndim, mass_coef=mass_coef)
+        L = len(cells)
+        self.maxiters = _smoother_counts(maxiters, L)
+        self.knots = knots = [uniform_knots(p, N) for N in cells]
+        self.P1 = [two_level_setup_1d(p, knots[l], knots[l + 1])[2] for l in range(L - 1)]
+        self.M1d, self.K1d = (list(f) for f in zip(*[assemble_1d(T, p) for T in knots]))
+        self.spaces, self.ops, self.transfers = [], [], []
+        for l in range(L - 1):
+            V = StencilVectorSpace([len(knots[l]) - p - 1] * ndim, [p] * ndim, dist=dist if l == 0 else None,
+                                   device=device, align=align)
+            A = KronOperator.laplace(V, [self.M1d[l]] * ndim, [self.K1d[l]] * ndim, mass_coef=mass_coef)
             if chunk:
                 A.set_chunk(chunk)
             self.spaces.append(V)
@@ -226,82 +283,18 @@ class MultilevelVCycle:
         if fused_restrict is None:
             fused_restrict = ndim == 3
         self.fused = [bool(fused_restrict) and tr.set_operator(A) for tr, A in zip(self.transfers, self.ops)]
-        # coarsest level: dense inverse of its operator (assembled = Galerkin, nested)
-        from .splines import band_to_dense
+        # coarsest level: its operator assembled on its knots (= Galerkin, nested)
         Mc, Kc = band_to_dense(self.M1d[-1]), band_to_dense(self.K1d[-1])
-        Ac = galerkin_coarse_dense(Mc, Kc, ndim, mass_coef)
-        self.Ac = Ac
-        Ainv = sla.lu_solve(sla.lu_factor(Ac), np.eye(Ac.shape[0]))
-        dev = f"cuda:{self.spaces[0].device}"
-        self.Ainv = torch.from_numpy(np.ascontiguousarray(Ainv)).to(dev)
-        self.rcs = [torch.empty(tr.ncoarse, dtype=F64, device=dev) for tr in self.transfers]
-        self.xc = torch.empty(Ac.shape[0], dtype=F64, device=dev)
-        self.infos = [None] * (L - 1)
-
-    @property
-    def ndof(self) -> int:
-        return self.spaces[0].dimension
-
-    @property
-    def space(self) -> StencilVectorSpace:
-        return self.spaces[0]
-
-    @property
-    def A(self) -> KronOperator:
-        return self.ops[0]
-
-    def rhs_ones(self) -> StencilVector:
-        b = self.spaces[0].empty()
-        _lib.call("poms_vec_fill", self.spaces[0].ctx, C.byref(self.spaces[0].layout), 1.0, rt.ptr(b._data),
-                  rt.stream_handle())
-        b._mark_written()
-        b.update_ghost_regions()
-        return b
-
-    def _level(self, l: int, b: StencilVector, x0: StencilVector | None) -> StencilVector:
-        A, tr = self.ops[l], self.transfers[l]
-        dx = defer_x_count(A, self.spaces[l], self.maxiters[l])
-        x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True,
-                      _defer_x=dx)
-        if self.fused[l]:
-            rc = tr.resid_restrict(A, b, x, out=self.rcs[l])
-        else:
-            rc = tr.restrict(A.residual(b, x), out=self.rcs[l])
-        if l + 1 == self.nlevels - 1:
-            ec = self.xc
-            _lib.call("poms_dense_matvec", self.spaces[0].ctx, rc.numel(), rt.ptr(self.Ainv), rt.ptr(rc),
-                      rt.ptr(ec), rt.stream_handle())
-        else:
-            Vc = self.spaces[l + 1]
-            bc = Vc.empty()
-            Vc.interior(bc._data).copy_(rc.view(Vc.local_npts))
-            bc._mark_written()
-            bc.update_ghost_regions()
-            ecv = self._level(l + 1, bc, None)
-            ec = Vc.interior(ecv._data).contiguous().view(-1)
-        tr.prolong_add(ec, x)
-        x.update_ghost_regions()
-        x, ipos = pcg(A, damped_jacobi, b, x0=x, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True,
-                      _defer_x=dx)
-        if self.infos[l] is None:
-            self.infos[l] = (ipre, ipos)
-        return x
-
-    def cycle(self, b: StencilVector, x0: StencilVector | None = None):
-        """One V-cycle from level 0; returns ``(x, infos)``, ``infos[l] = (info_pre,
-        info_post)`` of level l's first visit in this cycle."""
-        self.infos = [None] * (self.nlevels - 1)
-        x = self._level(0, b, x0)
-        return x, list(self.infos)
+        self._set_coarse(galerkin_coarse_dense(Mc, Kc, ndim, mass_coef))
 
 
-class GalerkinVCycle:
+class GalerkinVCycle(_VCycle):
     """V-cycle for a general (variable-coefficient) stencil operator with Galerkin
     coarse operators, as the reference builds its own (`sources/mg_jac.py:80-81`,
     ``Ac = R Af P`` of the assembled matrix): ``ops[l+1] = P_l^T ops[l] P_l`` formed on
     the device (:func:`~poms_amd.multilevels.galerkin_stencil`), every level smoothed
     by ``pcg(A_l, damped_jacobi, b_l, tol, maxiters[l])`` before and after the coarse
-    correction (:meth:`MultilevelVCycle._level`'s sequence; residual and restriction are
+    correction (the base's ``_level`` sequence; residual and restriction are
     two launches, there is no fused pass for stencils) and a dense solve on the
     coarsest level.
 
@@ -313,26 +306,17 @@ class GalerkinVCycle:
         if len(P) < 1:
             raise ValueError("the hierarchy needs at least two levels")
         self.tol = tol
-        self.nlevels = L = len(P) + 1
-        self.maxiters = [10] * (L - 1) if maxiters is None else [int(m) for m in maxiters]
-        if len(self.maxiters) != L - 1:
-            raise ValueError(f"maxiters needs {L - 1} entries")
+        self.maxiters = _smoother_counts(maxiters, len(P) + 1)
         self.P = [[np.ascontiguousarray(p, dtype=np.float64) for p in Pl] for Pl in P]
         self.ops, self.spaces, self.transfers = [A], [A.space], []
-        for l in range(L - 1):
+        for l in range(len(P)):
             Ac = self._coarse_op(l)
             self.transfers.append(KronTransfer(self.spaces[l], self.P[l]))
             self.ops.append(Ac)
             self.spaces.append(Ac.space)
-        # coarsest level: dense inverse of its Galerkin operator, applied on the device
-        Ac = self.ops[-1].toarray()
-        self.Ac = Ac
-        Ainv = sla.lu_solve(sla.lu_factor(Ac), np.eye(Ac.shape[0]))
-        dev = f"cuda:{self.spaces[0].device}"
-        self.Ainv = torch.from_numpy(np.ascontiguousarray(Ainv)).to(dev)
-        self.rcs = [torch.empty(tr.ncoarse, dtype=F64, device=dev) for tr in self.transfers]
-        self.xc = torch.empty(Ac.shape[0], dtype=F64, device=dev)
-        self.infos = [None] * (L - 1)
+        self.fused = [False] * len(P)
+        # coarsest level: its Galerkin operator, inverted densely
+        self._set_coarse(self.ops[-1].toarray())
 
     def _coarse_op(self, l: int):
         """Level ``l+1``'s operator from level ``l``'s (subclasses may rediscretise)."""
@@ -348,19 +332,9 @@ class GalerkinVCycle:
         :class:`~poms_amd.geometry.Mapping` or ``SplineMapping``): the operator of the
         mapped domain, its tensor sampled on the finest quadrature grid (``a`` / ``c``
         are then functions of the physical coordinates)."""
-        from .assembly import assemble_stencil
-        if ncells_fine < ncells_coarsest or ncells_coarsest < 1:
-            raise ValueError("need ncells_fine >= ncells_coarsest >= 1")
-        cells = [int(ncells_fine)]
-        while cells[-1] // 2 >= ncells_coarsest and cells[-1] % 2 == 0:
-            cells.append(cells[-1] // 2)
-        if len(cells) < 2:
-            raise ValueError("the hierarchy needs at least two levels (even cell counts)")
-        knots = [uniform_knots(p, N) for N in cells]
-        P1 = [two_level_setup_1d(p, knots[l], knots[l + 1])[2] for l in range(len(cells) - 1)]
-        V = StencilVectorSpace([len(knots[0]) - p - 1] * ndim, [p] * ndim, device=device, align=True)
+        from .assembly import assemble_stencil, axis_tables
+        cells, knots, P1, V = uniform_hierarchy(p, ncells_fine, ncells_coarsest, ndim, device)
         if mapping is not None:
-            from .assembly import axis_tables
             pts = axis_tables(knots[0], p)["points"].reshape(-1)
             a, c, _ = mapping.pullback([pts] * ndim, a=a, c=c, mass_coef=mass_coef, device=f"cuda:{V.device}")
         A = assemble_stencil(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef)
@@ -368,55 +342,3 @@ class GalerkinVCycle:
         mg.p, mg.ndim, mg.cells, mg.knots, mg.P1 = int(p), int(ndim), cells, knots, P1
         return mg
 
-    @property
-    def ndof(self) -> int:
-        return self.spaces[0].dimension
-
-    @property
-    def space(self) -> StencilVectorSpace:
-        return self.spaces[0]
-
-    @property
-    def A(self):
-        return self.ops[0]
-
-    def rhs_ones(self) -> StencilVector:
-        b = self.spaces[0].empty()
-        _lib.call("poms_vec_fill", self.spaces[0].ctx, C.byref(self.spaces[0].layout), 1.0, rt.ptr(b._data),
-                  rt.stream_handle())
-        b._mark_written()
-        b.update_ghost_regions()
-        return b
-
-    def _level(self, l: int, b: StencilVector, x0: StencilVector | None) -> StencilVector:
-        A, tr = self.ops[l], self.transfers[l]
-        dx = defer_x_count(A, self.spaces[l], self.maxiters[l])
-        x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True,
-                      _defer_x=dx)
-        rc = tr.restrict(A.residual(b, x), out=self.rcs[l])
-        if l + 1 == self.nlevels - 1:
-            ec = self.xc
-            _lib.call("poms_dense_matvec", self.spaces[0].ctx, rc.numel(), rt.ptr(self.Ainv), rt.ptr(rc),
-                      rt.ptr(ec), rt.stream_handle())
-        else:
-            Vc = self.spaces[l + 1]
-            bc = Vc.empty()
-            Vc.interior(bc._data).copy_(rc.view(Vc.local_npts))
-            bc._mark_written()
-            bc.update_ghost_regions()
-            ecv = self._level(l + 1, bc, None)
-            ec = Vc.interior(ecv._data).contiguous().view(-1)
-        tr.prolong_add(ec, x)
-        x.update_ghost_regions()
-        x, ipos = pcg(A, damped_jacobi, b, x0=x, tol=self.tol, maxiter=self.maxiters[l], _skip_tail=True,
-                      _defer_x=dx)
-        if self.infos[l] is None:
-            self.infos[l] = (ipre, ipos)
-        return x
-
-    def cycle(self, b: StencilVector, x0: StencilVector | None = None):
-        """One V-cycle from level 0; returns ``(x, infos)``, ``infos[l] = (info_pre,
-        info_post)`` of level l's first visit in this cycle."""
-        self.infos = [None] * (self.nlevels - 1)
-        x = self._level(0, b, x0)
-        return x, list(self.infos)

@@ -534,10 +534,17 @@ class KronOperator:
     natural BCs; 2D/1D analogues).  ``form='single'``: A = F0⊗F1⊗F2.
     """
 
-    def __init__(self, V: StencilVectorSpace, form: str, bands: dict, pmax: int):
+    def _init_base(self, V: StencilVectorSpace, form: str, bands: dict | None = None, pmax: int | None = None):
+        """The fields every operator form has (``_h`` is the form's own)."""
         self.space, self.form = V, form
-        self.pmax = int(pmax)
-        self.bands = bands  # host copies (global rows) by role name
+        self.pmax = max(max(V.pads), 1) if pmax is None else int(pmax)
+        self.bands = {} if bands is None else bands  # host copies (global rows) by role name
+        self.timer = None  # list -> (kind, start_event, end_event, call) per kernel launch
+        self._calls = 0    # operator calls (one call = 1 launch, or 2 when a halo exchange is overlapped)
+        self.pads, self.starts, self.ends = V.pads, V.starts, V.ends
+
+    def __init__(self, V: StencilVectorSpace, form: str, bands: dict, pmax: int):
+        self._init_base(V, form, bands, pmax)
         self._h = C.c_void_p()
         nd = V.ndim
         W = 2 * self.pmax + 1
@@ -584,8 +591,6 @@ class KronOperator:
             # rank (operators are built in the same order everywhere), not inside a capture
             d.native.peer_reserve(self.pmax * V.plane_elems, -1 if d.prev is None else d.prev,
                                   -1 if d.next is None else d.next)
-        self.timer = None  # list -> (kind, start_event, end_event, call) per kernel launch
-        self._calls = 0    # operator calls (one call = 1 launch, or 2 when a halo exchange is overlapped)
 
     # -- constructors ------------------------------------------------------------
     @classmethod
@@ -1068,27 +1073,18 @@ class StencilMatrix(KronOperator):
     def __init__(self, V: StencilVectorSpace, W: StencilVectorSpace | None = None):
         if W is not None and W is not V:
             raise NotImplementedError("rectangular stencil matrices are not supported")
-        self.space, self.form = V, "stencil"
-        self.pmax = max(max(V.pads), 1)
-        self.bands = {}
-        self.timer = None
-        self._calls = 0
+        self._init_base(V, "stencil")
         self._hh = C.c_void_p()
         self._dirty = True
         self._host = np.zeros(V.padded_shape + tuple(2 * p + 1 for p in V.pads))
-        self.pads = V.pads
-        self.starts, self.ends = V.starts, V.ends
 
     @classmethod
     def _from_handle(cls, V: StencilVectorSpace, h: C.c_void_p) -> "StencilMatrix":
         """Wrap a device-built general-stencil operator (``poms_op_assemble_stencil``);
         the host copy is fetched on first host-side access."""
         M = cls.__new__(cls)
-        M.space, M.form = V, "stencil"
-        M.pmax = max(max(V.pads), 1)
-        M.bands, M.timer, M._calls = {}, None, 0
+        M._init_base(V, "stencil")
         M._hh, M._dirty, M._host = h, False, None
-        M.pads, M.starts, M.ends = V.pads, V.starts, V.ends
         return M
 
     @property

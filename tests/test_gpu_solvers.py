@@ -201,6 +201,53 @@ def test_multilevel_converges_h_independently(gpu):
     assert rates[1] <= 2.0 * rates[0] + 0.05
 
 
+@pytest.mark.parametrize("which", ["two_level", "multilevel", "galerkin", "matfree"])
+def test_vcycle_leaves_x0_untouched(gpu, which):
+    """Every class runs the one shared level sequence, whose post-smoother iterates in
+    place (its x is the cycle's own temporary) and whose pre-smoother must not: level
+    0's x0 is the caller's.  A second cycle started from the first one's result leaves
+    that result as it was, bit for bit."""
+    import torch
+    from poms_amd.matfree import MatrixFreeVCycle
+    from poms_amd.mg import GalerkinVCycle, MultilevelVCycle, TwoLevelVCycle
+    mg = {"two_level": lambda: TwoLevelVCycle(2, 16, 4, ndim=2),
+          "multilevel": lambda: MultilevelVCycle(2, 16, 4, ndim=2),
+          "galerkin": lambda: GalerkinVCycle.uniform(2, 16, 4, 2),
+          "matfree": lambda: MatrixFreeVCycle.uniform(2, 16, 4, 2)}[which]()
+    b = mg.rhs_ones()
+    x = mg.cycle(b)[0]
+    before = x._data.clone()
+    x2 = mg.cycle(b, x0=x)[0]
+    assert torch.equal(x._data, before)
+    assert not torch.equal(x2._data, before)   # (the second cycle did run on)
+
+
+@pytest.mark.parametrize("ndim,p,Nf,Nc", [(2, 2, 16, 8), (3, 2, 8, 4)])
+def test_two_levels_through_either_class(gpu, ndim, p, Nf, Nc):
+    """A two-level hierarchy through TwoLevelVCycle (``Ac = P^T A P`` from the dense 1D
+    factors) and through MultilevelVCycle (the coarse operator assembled on its knots):
+    the same fine operator and launches, so the pre-smoother infos are equal; the
+    results agree with each other and with the oracle's recursive cycle within the
+    parity bound of :func:`test_multilevel_vcycle`.  Fixed counts (tol = 0): no stop
+    test that could move by one."""
+    from poms_amd.mg import MultilevelVCycle, TwoLevelVCycle
+    two = TwoLevelVCycle(p, Nf, Nc, ndim=ndim, tol=0.0, maxiter=3)
+    rec = MultilevelVCycle(p, Nf, Nc, ndim=ndim, tol=0.0, maxiters=[3])
+    assert rec.nlevels == 2
+    x2, ipre2, ipos2 = two.cycle(two.rhs_ones())
+    xm, infos = rec.cycle(rec.rhs_ones())
+    assert ipre2 == infos[0][0]
+    ones = np.ones((two.n,) * ndim)
+    Ms, Ks = [[rec.M1d[0]] * ndim], [[rec.K1d[0]] * ndim]
+    xr, rinfos = orc.vcycle_multilevel(Ms, Ks, rec.P1, ones, tol=0.0, maxiters=[3])
+    xr2, _ = orc.vcycle_multilevel(Ms, Ks, rec.P1, ones, tol=0.0, maxiters=[3], reorder=True)
+    tol = max(1e-9, 20.0 * rel(xr2, xr))
+    assert ipre2["niter"] == rinfos[0][0]["niter"] == 3 and ipos2["niter"] == infos[0][1]["niter"] == 3
+    assert rel(x2.to_local_numpy(), xr) <= tol
+    assert rel(xm.to_local_numpy(), xr) <= tol
+    assert rel(x2.to_local_numpy(), xm.to_local_numpy()) <= tol
+
+
 @pytest.mark.parametrize("ndim,p,Nf", [(2, 3, 80), (3, 2, 72)])
 def test_transfer_banded(gpu, ndim, p, Nf):
     """Restriction / prolongation with coarse extents > 32 (the banded gather kernels

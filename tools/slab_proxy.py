@@ -32,12 +32,10 @@ sys.path.insert(0, str(ROOT))
 
 def build(planes_cells: int, cells: int, p: int, coarse: int):
     import numpy as np
-    import scipy.linalg as sla
-    import torch
     from poms_amd.mg import TwoLevelVCycle, two_level_setup_1d
     from poms_amd.multilevels import KronTransfer
     from poms_amd.splines import assemble_1d, band_to_dense, uniform_knots
-    from poms_amd.stencil import F64, KronOperator, StencilVectorSpace
+    from poms_amd.stencil import KronOperator, StencilVectorSpace
 
     cells3 = (planes_cells, cells, cells)
     Ms, Ks, Ps, Mcs, Kcs = [], [], [], [], []
@@ -49,18 +47,15 @@ def build(planes_cells: int, cells: int, p: int, coarse: int):
         Mcs.append(P1.T @ Md @ P1), Kcs.append(P1.T @ Kd @ P1)
     npts = [m.shape[0] for m in Ms]
     mg = TwoLevelVCycle.__new__(TwoLevelVCycle)
-    mg.p, mg.ndim, mg.glt, mg.tol, mg.maxiter, mg.post_smoother = p, 3, None, 1e-6, 10, "jacobi"
-    mg.space = StencilVectorSpace(npts, [p] * 3, align=True)
-    mg.A = KronOperator.laplace(mg.space, Ms, Ks)
-    mg.transfer = KronTransfer(mg.space, Ps)
+    mg.p, mg.ndim, mg.glt, mg.tol, mg.maxiters, mg.post_smoother = p, 3, None, 1e-6, [10], "jacobi"
+    V = StencilVectorSpace(npts, [p] * 3, align=True)
+    mg.spaces, mg.ops, mg.transfers = [V], [KronOperator.laplace(V, Ms, Ks)], [KronTransfer(V, Ps)]
+    mg.fused = [mg.transfer.set_operator(mg.A)]   # (fused where it applies, as TwoLevelVCycle's 3D default)
     kr = lambda a, b, c: np.kron(np.kron(a, b), c)
     Ac = kr(Mcs[0], Mcs[1], Mcs[2])
     for d in range(3):
         Ac = Ac + kr(*[Kcs[e] if e == d else Mcs[e] for e in range(3)])
-    Ainv = sla.lu_solve(sla.lu_factor(Ac), np.eye(Ac.shape[0]))
-    mg.Ainv = torch.from_numpy(np.ascontiguousarray(Ainv)).to(f"cuda:{mg.space.device}")
-    mg.rc = torch.empty(Ac.shape[0], dtype=F64, device=mg.Ainv.device)
-    mg.xc = torch.empty(Ac.shape[0], dtype=F64, device=mg.Ainv.device)
+    mg._set_coarse(Ac)
     return mg, npts
 
 
