@@ -33,8 +33,9 @@
 extern "C" {
 #endif
 
-#define POMS_ABI_VERSION 7 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
-                            * 7: poms_pcg_opts.n_pbuf, .pbuf */
+#define POMS_ABI_VERSION 8 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
+                            * 7: poms_pcg_opts.n_pbuf, .pbuf;
+                            * 8: poms_op_set_dirichlet, poms_op_get_dirichlet */
 
 /* operator forms (see poms_op_create) */
 #define POMS_FORM_SINGLE 0 /* y = F0 (x) F1 (x) F2 x                                  */
@@ -648,6 +649,23 @@ int poms_op_timing(poms_op* op, int enable, int epilogue, int every, int reserve
  * step by step (a stop test fired), [2] graph captures, [3] graph replays of an
  * earlier capture.                                                                */
 int poms_op_spec_stats(poms_op* op, int* stats);
+/* Dirichlet (essential) boundary conditions on whole faces of a general-stencil or
+ * matrix-free operator.  `faces` has bit 2 d + side set (d < ndim in the operator's own
+ * axes; side 0: index 0, side 1: index n_d - 1) for every constrained face; C is the set
+ * of rows on such a face and Pi the 0/1 projection onto the others.  Every launch of the
+ * operator then applies A_D = Pi A Pi + (I - Pi) diag(A) (I - Pi) to any input: free
+ * rows leave out the terms whose neighbour is in C, rows in C take diag * x.  The stored
+ * coefficients and the stored diagonal stay those of A (poms_op_stencil_data,
+ * poms_op_diagonal, poms_op_galerkin_stencil do not see the mask); 0 restores A, and the
+ * mask may be changed freely between launches (captured graphs of poms_pcg_jacobi are
+ * re-keyed).  Refused: Kronecker forms (constrain their factors instead), slabs and
+ * Cart blocks, bits beyond 2 ndim, and a call while a stream capture is in progress, as
+ * far as the call can see one: it has no stream argument and asks the legacy stream
+ * (which answers for a global-mode capture of the thread) and the operator's own capture
+ * stream; a relaxed or thread-local capture on another stream is not seen, and there the
+ * caller must not change the mask between capture and replay.                          */
+int poms_op_set_dirichlet(poms_op* op, int faces);
+int poms_op_get_dirichlet(poms_op* op, int* faces);
 int poms_op_timing_read(poms_op* op, int epilogue, double* total_ms, int64_t* launches, int64_t* dofs);
 
 /* ---- spline fields on tensor point grids --------------------------------------- */

@@ -25,6 +25,7 @@ __all__ = [
     "galerkin_stencil", "GalerkinVCycle",
     "MatrixFreeOperator", "MatrixFreeVCycle",
     "Mapping", "SplineMapping", "MappedDomain", "pullback",
+    "DirichletBC",
 ]
 
 
@@ -66,6 +67,9 @@ def __getattr__(name):
     if name in ("Mapping", "SplineMapping", "MappedDomain", "pullback"):
         from . import geometry
         return getattr(geometry, name)
+    if name == "DirichletBC":
+        from .boundary import DirichletBC
+        return DirichletBC
     if name == "SlabDistribution":
         from .dist import SlabDistribution
         return SlabDistribution

@@ -214,14 +214,20 @@ def quadrature_args(V: StencilVectorSpace, knots, nquad: int | None = None):
 
 
 def assemble_stencil(V: StencilVectorSpace, knots, a=None, c=None, mass_coef: float = 1.0,
-                     nquad: int | None = None) -> StencilMatrix:
+                     nquad: int | None = None, dirichlet=None) -> StencilMatrix:
     """``-∇·(a ∇u) + c u`` on the tensor space of ``knots`` (one knot vector per axis,
     degree = the space's pads), assembled on the device.  ``a``/``c``: None (1 and
     ``mass_coef``), a callable of the quadrature-point coordinates (``meshgrid``,
     ``indexing='ij'``) or an array of the quadrature grid's shape.  ``a`` may be a
     tensor coefficient: an array, a float64 device tensor, or a callable returning
-    either, of shape ``(ncomp,) + quad_shape`` (see the module's text)."""
+    either, of shape ``(ncomp,) + quad_shape`` (see the module's text).  ``dirichlet``:
+    constrained faces, passed to ``set_dirichlet`` (the assembled coefficients are those
+    of the unconstrained operator)."""
     nd = V.ndim
+    if dirichlet is not None:   # (refused before anything is assembled)
+        from .boundary import normalize_faces
+        if normalize_faces(dirichlet, nd) is not None and (V.is_distributed or V.is_cart):
+            raise NotImplementedError("dirichlet: distributed (slab / Cart) spaces are not supported")
     tabs, tables, _keep = quadrature_args(V, knots, nquad)
     dev = f"cuda:{V.device}"
     avals, tensor = split_coef(a, tabs)
@@ -236,4 +242,7 @@ def assemble_stencil(V: StencilVectorSpace, knots, a=None, c=None, mass_coef: fl
     else:
         _lib.call("poms_op_assemble_stencil", V.ctx, nd, C.byref(V.layout), *tables,
                   None if aq is None else C.c_void_p(aq.data_ptr()), *tail)
-    return StencilMatrix._from_handle(V, h)
+    A = StencilMatrix._from_handle(V, h)
+    if dirichlet is not None:
+        A.set_dirichlet(dirichlet)
+    return A

@@ -65,7 +65,8 @@ struct poms_op {
     bool mf_tensor = false;
     double mf_mass = 1.0;
     poms::MatfreeGeom mf_geom{};
-    uint64_t gen = 0;   // bumped by every setter that changes the launches a graph would capture
+    int dmask = 0;      // general forms: Dirichlet faces in the kernels' axes (poms_op_set_dirichlet)
+    uint64_t gen = 0;  // bumped by every setter that changes the launches a graph would capture
     // op_run_split's interior launch: the communication stream's exchange and boundary
     // launch run beside it (the automatic chunking leaves them CUs, op_geom); written
     // by op_run_split only

@@ -756,6 +756,50 @@ int poms_op_spec_stats(poms_op* op, int* stats) {
     return 0;
 }
 
+// Dirichlet faces of a general form.  The mask is a run-time field of the launch
+// geometry; bumping `gen` re-keys the captured graphs of poms_pcg_jacobi (nothing else the
+// operator caches depends on what a launch computes).
+int poms_op_set_dirichlet(poms_op* op, int faces) {
+    const std::string fn = "poms_op_set_dirichlet: ";
+    if (!op) { set_error(fn + "null argument"); return 1; }
+    if (!general_form(op)) {
+        set_error(fn + "Kronecker forms are constrained through their factors (needs a general-stencil or matrix-free operator)");
+        return 1;
+    }
+    if (faces < 0 || faces >= (1 << (2 * op->ndim))) {
+        set_error(fn + "faces has bits beyond 2 ndim = " + std::to_string(2 * op->ndim));
+        return 1;
+    }
+    if (faces == 0 && op->dmask == 0) return 0;   // nothing to clear, on any layout
+    if (op->g0 != 0 || (op->ndim == 3 && op->L.n[0] != op->n0g) || (op->L.flags & POMS_LAYOUT_GHOST_DATA)) {
+        set_error(fn + "distributed operators (slabs, Cart blocks) are not supported");
+        return 1;
+    }
+    // (the legacy stream answers for a capture in progress on any stream of the thread
+    // in the global capture mode; the operator's own capture stream is asked as well)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    bool capturing = hipStreamIsCapturing(nullptr, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    if (!capturing && op->cap_stream)
+        capturing = hipStreamIsCapturing(op->cap_stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    if (capturing) {
+        (void)hipGetLastError();
+        set_error(fn + "called during a stream capture");
+        return 1;
+    }
+    const int m = faces << (2 * (3 - op->ndim));   // the operator's axes are the kernels' last ndim
+    if (m == op->dmask) return 0;
+    op->dmask = m;
+    op->mf_geom.dmask = m;
+    ++op->gen;
+    return 0;
+}
+
+int poms_op_get_dirichlet(poms_op* op, int* faces) {
+    if (!op || !faces) { set_error("poms_op_get_dirichlet: null argument"); return 1; }
+    *faces = op->dmask >> (2 * (3 - op->ndim));
+    return 0;
+}
+
 int poms_op_get_variant(poms_op* op, int* variant) {
     if (!op || !variant) { set_error("poms_op_get_variant: null argument"); return 1; }
     *variant = op->variant;
@@ -915,7 +959,7 @@ static int stencil_run(poms_op* o, int epi, double omega, const double* x, doubl
     if (zb < 0 || ze > r.n0 || zb > ze || zb2 < 0 || ze2 > r.n0 || zb2 > ze2) { set_error("general stencil: bad plane range"); return 1; }
     StencilGeom g{r.s0, r.s1, r.n0, r.n1, r.n2, r.pd0, r.pd1, r.pd2, o->sp[0], o->sp[1], o->sp[2],
                   2 * o->sp[0] + 1, 2 * o->sp[1] + 1, 2 * o->sp[2] + 1, (int64_t)r.n0 * r.n1 * r.n2,
-                  (int)zb, (int)ze, (int)zb2, (int)ze2};
+                  (int)zb, (int)ze, (int)zb2, (int)ze2, o->dmask};
     const int maxb = (int)(kScratch / 2);
     int nb = 0;
     double* scr = o->ctx->scratch;

@@ -57,6 +57,7 @@ struct StencilGeom {
     int w0, w1, w2;          // 2 p_d + 1 (1 on unused axes)
     int64_t cstride;         // doubles per coefficient plane (n0 n1 n2)
     int z_begin, z_end, z2_begin, z2_end;
+    int dmask;               // Dirichlet faces, bit 2 axis + side (0: none); needs the whole grid (n_d global)
 };
 
 // One axis of an on-device quadrature assembly (stencil_general.hip): elements
@@ -114,6 +115,7 @@ struct MatfreeGeom {
     int pd0, pd1, pd2;       // storage pads
     int tiles1, tiles2, nchunks, chunk;
     int64_t ntiles;          // tiles1 tiles2 nchunks
+    int dmask;               // Dirichlet faces, bit 2 axis + side (0: none)
 };
 
 // pcg's scalars folded into the flat vector updates (one rank, round 6): every block

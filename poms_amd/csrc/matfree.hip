@@ -58,7 +58,15 @@ int matfree_tile() { return MF_D; }
 int matfree_max_window() { return MF_W; }
 int matfree_max_elements() { return MF_E; }
 
-template <int EPI, bool TENSOR>
+// MASK builds apply Dirichlet faces (g.dmask, bit 2 axis + side): the constrained entries of
+// x enter the window as 0 and a constrained output row takes diag * x.  The face set is a
+// run-time field; MASK only says whether there is one, so that an operator without faces
+// runs the code it ran before the mask existed.  (As a run-time test alone the mask cost the
+// unmasked 2D apply 2 %: the kernel sits at the scalar-register limit, and the masked
+// blocks moved another hundred scalar reads and writes into vector lanes, 229 / 116 against
+// 136 / 69 in the scalar APPLY build.  The second set of builds adds 4 s to this file's
+// compilation, which runs beside kron_v5.hip's 280 s.)
+template <int EPI, bool TENSOR, bool MASK>
 __global__ void __launch_bounds__(256)
 matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1, const AssembleAxis A2,
                const double* __restrict__ x, double* __restrict__ y, const double* __restrict__ b,
@@ -150,6 +158,16 @@ matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1
                 if (inwin)
                     sX[(j % (p0 + 1)) * MF_WW + widx] =
                         x[(int64_t)(j + g.pd0) * g.s0 + (int64_t)(c1lo + wr + g.pd1) * g.s1 + (c2lo + wc + g.pd2)];
+            // Dirichlet faces: the constrained entries of the planes just loaded enter the
+            // window as 0 (every thread zeroes what it wrote itself)
+            if (MASK && inwin) {
+                const int c1 = c1lo + wr, c2 = c2lo + wc;
+                const bool fix12 = ((g.dmask & 4) && c1 == 0) || ((g.dmask & 8) && c1 == g.n1 - 1) ||
+                                   ((g.dmask & 16) && c2 == 0) || ((g.dmask & 32) && c2 == g.n2 - 1);
+                for (int j = max(xnext, f0); j <= f0 + p0; ++j)
+                    if (fix12 || ((g.dmask & 1) && j == 0) || ((g.dmask & 2) && j == g.n0 - 1))
+                        sX[(j % (p0 + 1)) * MF_WW + widx] = 0.0;
+            }
             xnext = f0 + p0 + 1;
             __syncthreads();
             for (int q0 = 0; q0 < nq0; ++q0) {
@@ -283,9 +301,14 @@ matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1
             while (jf < z1 && A0.ee[jf] <= e0) {
                 if (own) {
                     const int i1 = i1lo + i1l, i2 = i2lo + i2l;
-                    const double s = sY[(jf % (p0 + 1)) * MF_DD + tid];
+                    double s = sY[(jf % (p0 + 1)) * MF_DD + tid];
                     sY[(jf % (p0 + 1)) * MF_DD + tid] = 0.0;
                     const int64_t xo = (int64_t)(jf + g.pd0) * g.s0 + (int64_t)(i1 + g.pd1) * g.s1 + (i2 + g.pd2);
+                    // a constrained row applies its diagonal entry only
+                    if (MASK && (((g.dmask & 1) && jf == 0) || ((g.dmask & 2) && jf == g.n0 - 1) ||
+                                    ((g.dmask & 4) && i1 == 0) || ((g.dmask & 8) && i1 == g.n1 - 1) ||
+                                    ((g.dmask & 16) && i2 == 0) || ((g.dmask & 32) && i2 == g.n2 - 1)))
+                        s = diag[((int64_t)jf * g.n1 + i1) * g.n2 + i2] * x[xo];
                     if constexpr (EPI == EPI_APPLY) {
                         y[xo] = s;
                     } else if constexpr (EPI == EPI_RESID) {
@@ -394,10 +417,12 @@ int matfree_diag_launch(const AssembleAxis* ax, const double* a_q, const double*
 // any number of registers up to 256 keeps that, scratch does not.  False, with a
 // message, if a build reports scratch or the attributes cannot be read.
 bool matfree_tensor_builds_ok(std::string* why) {
-    const void* fns[4] = {(const void*)matfree_kernel<EPI_APPLY, true>, (const void*)matfree_kernel<EPI_RESID, true>,
-                          (const void*)matfree_kernel<EPI_JACOBI, true>,
-                          (const void*)matfree_kernel<EPI_APPLYDOT, true>};
-    for (int k = 0; k < 4; ++k) {
+    const void* fns[8] = {
+        (const void*)matfree_kernel<EPI_APPLY, true, false>, (const void*)matfree_kernel<EPI_RESID, true, false>,
+        (const void*)matfree_kernel<EPI_JACOBI, true, false>, (const void*)matfree_kernel<EPI_APPLYDOT, true, false>,
+        (const void*)matfree_kernel<EPI_APPLY, true, true>, (const void*)matfree_kernel<EPI_RESID, true, true>,
+        (const void*)matfree_kernel<EPI_JACOBI, true, true>, (const void*)matfree_kernel<EPI_APPLYDOT, true, true>};
+    for (int k = 0; k < 8; ++k) {
         hipFuncAttributes at{};
         if (hipFuncGetAttributes(&at, fns[k]) != hipSuccess) {
             (void)hipGetLastError();
@@ -421,14 +446,15 @@ int matfree_launch(int epi, const MatfreeGeom& g, const AssembleAxis* ax, const 
     const int nb = (int)std::min<int64_t>(g.ntiles, max_blocks);
     *nblk_out = nb;
     if (nb <= 0) return 0;
+#define POMS_MF_LAUNCH1(E, T, M)                                                                              \
+    hipLaunchKernelGGL((matfree_kernel<E, T, M>), dim3(nb), dim3(256), 0, st, g, ax[0], ax[1], ax[2], x, y, b, a_q,  \
+                       c_q, diag, mass_coef, omega, partial, partial2)
 #define POMS_MF_LAUNCH(E)                                                                                     \
     do {                                                                                                      \
-        if (tensor)                                                                                           \
-            hipLaunchKernelGGL((matfree_kernel<E, true>), dim3(nb), dim3(256), 0, st, g, ax[0], ax[1], ax[2], x, y, \
-                               b, a_q, c_q, diag, mass_coef, omega, partial, partial2);                       \
-        else                                                                                                  \
-            hipLaunchKernelGGL((matfree_kernel<E, false>), dim3(nb), dim3(256), 0, st, g, ax[0], ax[1], ax[2], x, y, \
-                               b, a_q, c_q, diag, mass_coef, omega, partial, partial2);                       \
+        if (tensor && g.dmask) POMS_MF_LAUNCH1(E, true, true);                                                \
+        else if (tensor) POMS_MF_LAUNCH1(E, true, false);                                                     \
+        else if (g.dmask) POMS_MF_LAUNCH1(E, false, true);                                                    \
+        else POMS_MF_LAUNCH1(E, false, false);                                                                \
     } while (0)
     switch (epi) {
         case EPI_APPLY: POMS_MF_LAUNCH(EPI_APPLY); break;
@@ -440,6 +466,7 @@ int matfree_launch(int epi, const MatfreeGeom& g, const AssembleAxis* ax, const 
             return 1;
     }
 #undef POMS_MF_LAUNCH
+#undef POMS_MF_LAUNCH1
     return 0;
 }
 

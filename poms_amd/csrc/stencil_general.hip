@@ -17,8 +17,10 @@
 
 namespace poms {
 
+// (amdgpu_num_sgpr: with the face offsets the kernel would take 106 scalar registers and
+// lose the eighth wave per SIMD; at 96 it keeps it, six to ten scalars living in vector lanes)
 template <int EPI>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96)))
 stencil_kernel(const StencilGeom g, const double* __restrict__ coef, const double* __restrict__ x,
                double* __restrict__ y, const double* __restrict__ b, double omega,
                double* __restrict__ partial, double* __restrict__ partial2) {
@@ -49,11 +51,44 @@ stencil_kernel(const StencilGeom g, const double* __restrict__ coef, const doubl
         }
         double s = 0.0;
         int k = 0;
-        for (int k0 = 0; k0 < g.w0; ++k0) {
-            const double* xr0 = x + xo + (int64_t)(k0 - g.p0) * g.s0;
-            for (int k1 = 0; k1 < g.w1; ++k1) {
-                const double* xr = xr0 + (int64_t)(k1 - g.p1) * g.s1 - g.p2;
-                for (int k2 = 0; k2 < g.w2; ++k2, ++k) s = fma(coef[k * g.cstride + lin], xr[k2], s);
+        // Dirichlet faces (g.dmask): per axis the stencil offset whose neighbour lies on a
+        // constrained face (no offset of the row matches where there is none).  The row itself
+        // is constrained when that offset is the centre and takes its diagonal term; a free
+        // row takes the neighbours on a constrained face as 0.  The choice between the two
+        // loops is uniform over the launch: rows near a face and rows far from every face
+        // share their waves (a row of the grid is shorter than a few waves), so a choice per
+        // row would run most waves through both loops.
+        if (g.dmask) {
+            int kl0 = -1, kh0 = -1, kl1 = -1, kh1 = -1, kl2 = -1, kh2 = -1;
+            if (g.dmask & 1) kl0 = g.p0 - (int)z;
+            if (g.dmask & 2) kh0 = g.n0 - 1 - (int)z + g.p0;
+            if (g.dmask & 4) kl1 = g.p1 - (int)i1;
+            if (g.dmask & 8) kh1 = g.n1 - 1 - (int)i1 + g.p1;
+            if (g.dmask & 16) kl2 = g.p2 - (int)i2;
+            if (g.dmask & 32) kh2 = g.n2 - 1 - (int)i2 + g.p2;
+            if (kl0 == g.p0 || kh0 == g.p0 || kl1 == g.p1 || kh1 == g.p1 || kl2 == g.p2 || kh2 == g.p2) {
+                s = coef[kc * g.cstride + lin] * x[xo];
+            } else {
+                for (int k0 = 0; k0 < g.w0; ++k0) {
+                    const double* xr0 = x + xo + (int64_t)(k0 - g.p0) * g.s0;
+                    const bool c0 = k0 == kl0 || k0 == kh0;
+                    for (int k1 = 0; k1 < g.w1; ++k1) {
+                        const double* xr = xr0 + (int64_t)(k1 - g.p1) * g.s1 - g.p2;
+                        const bool c1 = c0 || k1 == kl1 || k1 == kh1;
+                        for (int k2 = 0; k2 < g.w2; ++k2, ++k) {
+                            const double xv = xr[k2];
+                            s = fma(coef[k * g.cstride + lin], (c1 || k2 == kl2 || k2 == kh2) ? 0.0 : xv, s);
+                        }
+                    }
+                }
+            }
+        } else {
+            for (int k0 = 0; k0 < g.w0; ++k0) {
+                const double* xr0 = x + xo + (int64_t)(k0 - g.p0) * g.s0;
+                for (int k1 = 0; k1 < g.w1; ++k1) {
+                    const double* xr = xr0 + (int64_t)(k1 - g.p1) * g.s1 - g.p2;
+                    for (int k2 = 0; k2 < g.w2; ++k2, ++k) s = fma(coef[k * g.cstride + lin], xr[k2], s);
+                }
             }
         }
         if constexpr (EPI == EPI_APPLY) {

@@ -206,15 +206,22 @@ class MappedDomain:
         """``(G, gamma, det)`` at the quadrature points."""
         return self.mapping.pullback(self.points, a=a, c=c, mass_coef=mass_coef, device=self._dev)
 
-    def operator(self, a=None, c=None, mass_coef: float = 1.0, matrix_free: bool = False):
+    def operator(self, a=None, c=None, mass_coef: float = 1.0, matrix_free: bool = False, dirichlet=None):
         """``-∇·(a∇u) + c u`` on the physical domain, as the stored stencil or
-        (``matrix_free``) a :class:`~poms_amd.matfree.MatrixFreeOperator`."""
+        (``matrix_free``) a :class:`~poms_amd.matfree.MatrixFreeOperator`; ``dirichlet``:
+        its constrained faces (:mod:`poms_amd.boundary`)."""
         G, gamma, _ = self.pullback(a, c, mass_coef)
         if matrix_free:
             from .matfree import MatrixFreeOperator
-            return MatrixFreeOperator(self.space, self.knots, a=G, c=gamma, nquad=self.nquad)
+            return MatrixFreeOperator(self.space, self.knots, a=G, c=gamma, nquad=self.nquad, dirichlet=dirichlet)
         from .assembly import assemble_stencil
-        return assemble_stencil(self.space, self.knots, a=G, c=gamma, nquad=self.nquad)
+        return assemble_stencil(self.space, self.knots, a=G, c=gamma, nquad=self.nquad, dirichlet=dirichlet)
+
+    def dirichlet(self, faces):
+        """The :class:`~poms_amd.boundary.DirichletBC` of the domain: boundary data as a
+        function of the physical coordinates."""
+        from .boundary import DirichletBC
+        return DirichletBC(self.space, self.knots, faces, mapping=self.mapping)
 
     def _setup(self):
         if self._quad is None:

@@ -76,10 +76,12 @@ class MatrixFreeOperator(KronOperator):
     ``dot``, ``residual``, ``dot_inner``, ``jacobi_sweep`` and ``diag_scale`` run the
     kernel's epilogues; ``pcg``, ``damped_jacobi``, ``jacobi`` and ``crl`` take the
     operator unchanged.  :meth:`assemble` gives the stored stencil of the same
-    arguments for cross-checks."""
+    arguments for cross-checks.  ``dirichlet`` / :meth:`set_dirichlet`: constrained faces
+    (:mod:`poms_amd.boundary`); the stored diagonal stays that of the unconstrained
+    operator."""
 
     def __init__(self, V: StencilVectorSpace, knots, a=None, c=None, mass_coef: float = 1.0,
-                 nquad: int | None = None):
+                 nquad: int | None = None, dirichlet=None):
         if V.is_cart or V.is_distributed or tuple(V.local_npts) != tuple(V.npts):
             raise NotImplementedError("matrix-free operators are implemented for undistributed spaces "
                                       "(no slab or Cart decomposition)")
@@ -107,6 +109,8 @@ class MatrixFreeOperator(KronOperator):
                           None if self._aq is None else C.c_void_p(self._aq.data_ptr()), *tail)
         except _lib.PomsError as e:
             raise ValueError(str(e)) from None
+        if dirichlet is not None:
+            self.set_dirichlet(dirichlet)
 
     def diagonal(self) -> torch.Tensor:
         """diag(A) of the interior rows as a device tensor of the grid's shape (the
@@ -133,7 +137,7 @@ class MatrixFreeOperator(KronOperator):
         to_np = lambda f: f.cpu().numpy() if isinstance(f, torch.Tensor) else f
         # (a tensor coefficient goes on as the device array the operator holds)
         return assemble_stencil(self.space, self.knots, a=self._aq if self.tensor else to_np(a), c=to_np(c),
-                                mass_coef=self.mass_coef, nquad=self.nquad)
+                                mass_coef=self.mass_coef, nquad=self.nquad, dirichlet=self.dirichlet)
 
     def _no_matrix(self, what):
         raise NotImplementedError(f"a matrix-free operator stores no coefficients: {what} is not available; "
@@ -183,7 +187,7 @@ class MatrixFreeVCycle(GalerkinVCycle):
     @classmethod
     def uniform(cls, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *, a=None, c=None,
                 mass_coef: float = 1.0, nquad: int | None = None, device=None, tol: float = 1e-6, maxiters=None,
-                mapping=None):
+                mapping=None, dirichlet=None):
         """Dyadic uniform hierarchy, as :meth:`GalerkinVCycle.uniform`.  ``a`` / ``c``:
         None, scalars or callables (they are sampled on two quadrature grids, the
         finest level's and level 1's).  ``mapping``: the operator of the mapped domain
@@ -198,7 +202,7 @@ class MatrixFreeVCycle(GalerkinVCycle):
             pull = lambda T: mapping.pullback([axis_tables(T, p, nquad)["points"].reshape(-1)] * ndim, a=a, c=c,
                                               mass_coef=mass_coef, device=f"cuda:{V.device}")[:2]
             (a, c), (a1, c1) = pull(knots[0]), pull(knots[1])
-        A = MatrixFreeOperator(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef, nquad=nquad)
+        A = MatrixFreeOperator(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef, nquad=nquad, dirichlet=dirichlet)
         V1 = StencilVectorSpace([len(knots[1]) - p - 1] * ndim, [p] * ndim, device=V.device, align=True)
         A1 = assemble_stencil(V1, [knots[1]] * ndim, a=a1, c=c1, mass_coef=mass_coef, nquad=nquad)
         mg = cls(A, [[P1l] * ndim for P1l in P1], A1, tol=tol, maxiters=maxiters)

@@ -39,6 +39,7 @@ import torch
 
 from . import _lib
 from . import runtime as rt
+from .boundary import check_unit_rows, constrain_dense, constrain_prolongation, normalize_faces
 from .multilevels import KronTransfer, knots_to_insert
 from .solvers import damped_jacobi, defer_x_count, pcg, pcg_kron
 from .splines import (array_to_mat_stencil, assemble_1d, band_to_dense, collocation_cardinal_splines,
@@ -56,17 +57,20 @@ def two_level_setup_1d(p: int, Tf: np.ndarray, Tc: np.ndarray):
     return T, Ts, P1
 
 
-def galerkin_coarse_dense(Mc: np.ndarray, Kc: np.ndarray, ndim: int, mass_coef: float = 1.0) -> np.ndarray:
-    """Dense ``Ac = c Mc⊗Mc(⊗Mc) + Σ_d (Kc on axis d, Mc elsewhere)``."""
+def galerkin_coarse_dense(Mc, Kc, ndim: int, mass_coef: float = 1.0) -> np.ndarray:
+    """Dense ``Ac = c Mc⊗Mc(⊗Mc) + Σ_d (Kc on axis d, Mc elsewhere)``; ``Mc`` / ``Kc``: one
+    matrix for every axis, or a list of one per axis."""
     def kr(ms):
         out = ms[0]
         for m in ms[1:]:
             out = np.kron(out, m)
         return out
 
-    A = mass_coef * kr([Mc] * ndim)
+    Mc = list(Mc) if isinstance(Mc, (list, tuple)) else [Mc] * ndim
+    Kc = list(Kc) if isinstance(Kc, (list, tuple)) else [Kc] * ndim
+    A = mass_coef * kr(Mc)
     for d in range(ndim):
-        A = A + kr([Kc if e == d else Mc for e in range(ndim)])
+        A = A + kr([Kc[e] if e == d else Mc[e] for e in range(ndim)])
     return A
 
 
@@ -91,6 +95,25 @@ def uniform_hierarchy(p: int, ncells_fine: int, ncells_coarsest: int, ndim: int,
     P1 = [two_level_setup_1d(p, knots[l], knots[l + 1])[2] for l in range(len(cells) - 1)]
     V = StencilVectorSpace([len(knots[0]) - p - 1] * ndim, [p] * ndim, device=device, align=True)
     return cells, knots, P1, V
+
+
+def _constrained_P(P, faces):
+    """The per-axis prolongations the transfers of a constrained hierarchy are built from:
+    ``P_d Π_cd`` after :func:`~poms_amd.boundary.check_unit_rows` (``P`` itself without faces)."""
+    if faces is None:
+        return list(P)
+    check_unit_rows(P, faces)
+    return [constrain_prolongation(Pd, lo, hi) for Pd, (lo, hi) in zip(P, faces)]
+
+
+def _kron_dirichlet(dirichlet, ndim: int, dist, post_smoother: str = "jacobi"):
+    """The faces of a Kronecker V-cycle, after the combinations it does not implement."""
+    faces = normalize_faces(dirichlet, ndim)
+    if faces is not None and dist is not None:
+        raise NotImplementedError("dirichlet: distributed (slab / Cart) V-cycles are not supported")
+    if faces is not None and post_smoother == "glt":
+        raise NotImplementedError("dirichlet: the GLT post-smoother is not supported")
+    return faces
 
 
 def _smoother_counts(maxiters, nlevels: int) -> list:
@@ -195,11 +218,14 @@ class TwoLevelVCycle(_VCycle):
     def __init__(self, p: int, ncells_fine: int, ncells_coarse: int = 8, ndim: int = 3, *,
                  dist=None, mass_coef: float = 1.0, device=None, knots_fine=None, knots_coarse=None,
                  tol: float = 1e-6, maxiter: int = 10, chunk: int = 0, align: bool = True,
-                 post_smoother: str = "jacobi", fused_restrict: bool | None = None):
+                 post_smoother: str = "jacobi", fused_restrict: bool | None = None, dirichlet=None):
         self.p, self.ndim = int(p), int(ndim)
         if post_smoother not in ("jacobi", "glt"):
             raise ValueError("post_smoother must be 'jacobi' (mg_jac.py) or 'glt' (mg_glt.py)")
         self.post_smoother = post_smoother
+        # Dirichlet faces: constrained 1D factors on both levels, transfers from P Π_c, and
+        # the coarse factors constrain(P^T F P) (not (PΠ)^T F~ (PΠ), which is singular)
+        self.dirichlet = faces = _kron_dirichlet(dirichlet, ndim, dist, post_smoother)
         Tc = uniform_knots(p, ncells_coarse) if knots_coarse is None else np.asarray(knots_coarse, float)
         Tf = uniform_knots(p, ncells_fine) if knots_fine is None else np.asarray(knots_fine, float)
         T, Ts, P1 = two_level_setup_1d(p, Tf, Tc)
@@ -209,10 +235,10 @@ class TwoLevelVCycle(_VCycle):
         # line-aligned rows (pitch a multiple of 16 doubles): the v5 operator kernel
         # then stores whole 128-B lines only
         V = StencilVectorSpace([n] * ndim, [p] * ndim, dist=dist, device=device, align=align)
-        A = KronOperator.laplace(V, [M] * ndim, [K] * ndim, mass_coef=mass_coef)
+        A = KronOperator.laplace(V, [M] * ndim, [K] * ndim, mass_coef=mass_coef, dirichlet=faces)
         if chunk:
             A.set_chunk(chunk)
-        self.spaces, self.ops, self.transfers = [V], [A], [KronTransfer(V, [P1] * ndim)]
+        self.spaces, self.ops, self.transfers = [V], [A], [KronTransfer(V, _constrained_P([P1] * ndim, faces))]
         # residual -> restriction in one pass over x and b (KronTransfer.resid_restrict);
         # False: the residual vector and the restriction, as the reference computes them.
         # None: fused in 3D (515^3: 0.70 ms against 0.92 for the pair), not in 2D, where
@@ -222,7 +248,11 @@ class TwoLevelVCycle(_VCycle):
             fused_restrict = fr == "all" or (ndim == 3 and fr != "0")
         self.fused = [bool(fused_restrict) and self.transfer.set_operator(A)]
         Md, Kd = band_to_dense(M), band_to_dense(K)
-        self._set_coarse(galerkin_coarse_dense(P1.T @ Md @ P1, P1.T @ Kd @ P1, ndim, mass_coef))
+        Mc, Kc = [P1.T @ Md @ P1] * ndim, [P1.T @ Kd @ P1] * ndim
+        if faces is not None:
+            Mc = [constrain_dense(m, m.shape[:1], [f]) for m, f in zip(Mc, faces)]
+            Kc = [constrain_dense(k, k.shape[:1], [f]) for k, f in zip(Kc, faces)]
+        self._set_coarse(galerkin_coarse_dense(Mc, Kc, ndim, mass_coef))
         self.tol, self.maxiters = tol, [maxiter]
         if post_smoother == "glt":
             Cm = array_to_mat_stencil(n, p, collocation_cardinal_splines(p, n))
@@ -260,8 +290,9 @@ class MultilevelVCycle(_VCycle):
 
     def __init__(self, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *,
                  dist=None, mass_coef: float = 1.0, device=None, tol: float = 1e-6, maxiters=None,
-                 align: bool = True, chunk: int = 0, fused_restrict: bool | None = None):
+                 align: bool = True, chunk: int = 0, fused_restrict: bool | None = None, dirichlet=None):
         self.cells = cells = dyadic_cells(ncells_fine, ncells_coarsest)
+        self.dirichlet = faces = _kron_dirichlet(dirichlet, ndim, dist)   # (as TwoLevelVCycle)
         self.p, self.ndim, self.tol = int(p), int(ndim), tol
         L = len(cells)
         self.maxiters = _smoother_counts(maxiters, L)
@@ -272,19 +303,23 @@ class MultilevelVCycle(_VCycle):
         for l in range(L - 1):
             V = StencilVectorSpace([len(knots[l]) - p - 1] * ndim, [p] * ndim, dist=dist if l == 0 else None,
                                    device=device, align=align)
-            A = KronOperator.laplace(V, [self.M1d[l]] * ndim, [self.K1d[l]] * ndim, mass_coef=mass_coef)
+            A = KronOperator.laplace(V, [self.M1d[l]] * ndim, [self.K1d[l]] * ndim, mass_coef=mass_coef,
+                                     dirichlet=faces)
             if chunk:
                 A.set_chunk(chunk)
             self.spaces.append(V)
             self.ops.append(A)
-            self.transfers.append(KronTransfer(V, [self.P1[l]] * ndim))
+            self.transfers.append(KronTransfer(V, _constrained_P([self.P1[l]] * ndim, faces)))
         # fused residual -> restriction where the transfer is dense (coarse extents <= 32);
         # None: in 3D (as TwoLevelVCycle)
         if fused_restrict is None:
             fused_restrict = ndim == 3
         self.fused = [bool(fused_restrict) and tr.set_operator(A) for tr, A in zip(self.transfers, self.ops)]
         # coarsest level: its operator assembled on its knots (= Galerkin, nested)
-        Mc, Kc = band_to_dense(self.M1d[-1]), band_to_dense(self.K1d[-1])
+        Mc, Kc = [band_to_dense(self.M1d[-1])] * ndim, [band_to_dense(self.K1d[-1])] * ndim
+        if faces is not None:
+            Mc = [constrain_dense(m, m.shape[:1], [f]) for m, f in zip(Mc, faces)]
+            Kc = [constrain_dense(k, k.shape[:1], [f]) for k, f in zip(Kc, faces)]
         self._set_coarse(galerkin_coarse_dense(Mc, Kc, ndim, mass_coef))
 
 
@@ -300,6 +335,12 @@ class GalerkinVCycle(_VCycle):
 
     ``A``: the finest :class:`~poms_amd.stencil.StencilMatrix`; ``P[l]``: the list of
     1D prolongations, one per axis, from level ``l+1`` to level ``l``.
+
+    A constrained ``A`` (``A.dirichlet``) constrains the hierarchy: every coarse operator
+    gets the same faces, the transfers are built from ``P Π_c`` and the coarsest inverse
+    from the constrained dense matrix.  The Galerkin products still run on the stored
+    coefficients with the full ``P``: where the boundary rows of ``P`` are unit vectors
+    (checked), ``Π_c (PᵀAP) Π_c = (PΠ_c)ᵀ (Π_f A Π_f) (PΠ_c)``.
     """
 
     def __init__(self, A, P, *, tol: float = 1e-6, maxiters=None):
@@ -309,9 +350,13 @@ class GalerkinVCycle(_VCycle):
         self.maxiters = _smoother_counts(maxiters, len(P) + 1)
         self.P = [[np.ascontiguousarray(p, dtype=np.float64) for p in Pl] for Pl in P]
         self.ops, self.spaces, self.transfers = [A], [A.space], []
+        self.dirichlet = faces = A.dirichlet
         for l in range(len(P)):
+            Pt = _constrained_P(self.P[l], faces)
             Ac = self._coarse_op(l)
-            self.transfers.append(KronTransfer(self.spaces[l], self.P[l]))
+            if Ac.dirichlet != faces:
+                Ac.set_dirichlet(faces)
+            self.transfers.append(KronTransfer(self.spaces[l], Pt))
             self.ops.append(Ac)
             self.spaces.append(Ac.space)
         self.fused = [False] * len(P)
@@ -325,7 +370,8 @@ class GalerkinVCycle(_VCycle):
 
     @classmethod
     def uniform(cls, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *, a=None, c=None,
-                mass_coef: float = 1.0, device=None, tol: float = 1e-6, maxiters=None, mapping=None):
+                mass_coef: float = 1.0, device=None, tol: float = 1e-6, maxiters=None, mapping=None,
+                dirichlet=None):
         """Dyadic uniform hierarchy (as :class:`MultilevelVCycle`'s) under
         ``-∇·(a∇u) + c u`` assembled on the finest knots by
         :func:`~poms_amd.assembly.assemble_stencil`.  ``mapping`` (a
@@ -337,7 +383,7 @@ class GalerkinVCycle(_VCycle):
         if mapping is not None:
             pts = axis_tables(knots[0], p)["points"].reshape(-1)
             a, c, _ = mapping.pullback([pts] * ndim, a=a, c=c, mass_coef=mass_coef, device=f"cuda:{V.device}")
-        A = assemble_stencil(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef)
+        A = assemble_stencil(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef, dirichlet=dirichlet)
         mg = cls(A, [[P1l] * ndim for P1l in P1], tol=tol, maxiters=maxiters)
         mg.p, mg.ndim, mg.cells, mg.knots, mg.P1 = int(p), int(ndim), cells, knots, P1
         return mg

@@ -32,7 +32,7 @@ import numpy as np
 __all__ = [
     "make_open_knots", "uniform_knots", "find_span", "basis_funs_ders",
     "assemble_1d", "band_to_dense", "dense_to_band", "insert_knot_matrix",
-    "matrix_multi_stages", "greville",
+    "matrix_multi_stages", "greville", "constrain_1d",
 ]
 
 
@@ -223,6 +223,25 @@ def dense_to_band(A: np.ndarray, p: int) -> np.ndarray:
             j = i + k - p
             if 0 <= j < n:
                 band[i, k] = A[i, j]
+    return band
+
+
+def constrain_1d(band: np.ndarray, lo: bool, hi: bool) -> np.ndarray:
+    """``F̃ = Π₁ F Π₁ + (I − Π₁) diag(F) (I − Π₁)`` in band form: the first (``lo``) and /
+    or last (``hi``) row and column of the 1D factor reduced to their diagonal entry
+    (Dirichlet faces of a Kronecker operator, :mod:`poms_amd.boundary`)."""
+    band = np.array(band, dtype=np.float64, order="C")
+    n, w = band.shape
+    p = (w - 1) // 2
+    for on, r in ((lo, 0), (hi, n - 1)):
+        if not on:
+            continue
+        d = band[r, p]
+        band[r, :] = 0.0
+        band[r, p] = d
+        for i in range(max(0, r - p), min(n, r + p + 1)):   # column r: F[i, r] = band[i, r - i + p]
+            if i != r:
+                band[i, r - i + p] = 0.0
     return band
 
 

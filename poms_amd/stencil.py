@@ -542,6 +542,38 @@ class KronOperator:
         self.timer = None  # list -> (kind, start_event, end_event, call) per kernel launch
         self._calls = 0    # operator calls (one call = 1 launch, or 2 when a halo exchange is overlapped)
         self.pads, self.starts, self.ends = V.pads, V.starts, V.ends
+        self._dirichlet = None   # constrained faces ((lo, hi) per axis), see poms_amd.boundary
+
+    # -- Dirichlet faces ---------------------------------------------------------
+    @property
+    def dirichlet(self):
+        """The constrained faces, one ``(lo, hi)`` pair per axis, or None."""
+        return self._dirichlet
+
+    def set_dirichlet(self, faces) -> None:
+        """Constrain whole faces of a general form (``poms_op_set_dirichlet``): every
+        launch then applies ``Π A Π + (I − Π) diag(A) (I − Π)``; ``None`` restores ``A``.
+        ``faces``: see :func:`poms_amd.boundary.normalize_faces`.  Kronecker operators are
+        constrained through their factors (``KronOperator.laplace(..., dirichlet=)``)."""
+        from .boundary import normalize_faces
+        if self.form not in ("stencil", "matfree"):
+            raise NotImplementedError("a Kronecker operator is constrained through its factors: build it with "
+                                      "KronOperator.laplace(..., dirichlet=)")
+        V = self.space
+        f = normalize_faces(faces, V.ndim)
+        if f is not None and (V.is_distributed or V.is_cart or tuple(V.local_npts) != tuple(V.npts)):
+            raise NotImplementedError("dirichlet: distributed (slab / Cart) spaces are not supported")
+        if f is None and self._dirichlet is None:
+            return   # (nothing to clear: no handle is made or asked)
+        self._push_dirichlet(self._h, f)   # (a refusal leaves the faces as they were)
+        self._dirichlet = f
+
+    def _push_dirichlet(self, h, faces) -> None:
+        from .boundary import faces_mask
+        try:
+            _lib.call("poms_op_set_dirichlet", h, faces_mask(faces, self.space.ndim))
+        except _lib.PomsError as e:
+            raise ValueError(str(e)) from None
 
     def __init__(self, V: StencilVectorSpace, form: str, bands: dict, pmax: int):
         self._init_base(V, form, bands, pmax)
@@ -594,13 +626,25 @@ class KronOperator:
 
     # -- constructors ------------------------------------------------------------
     @classmethod
-    def laplace(cls, V: StencilVectorSpace, M: Sequence, K: Sequence, mass_coef: float = 1.0):
-        """-Δu + c u in Kronecker-sum form from per-axis 1D (mass, stiffness) bands."""
+    def laplace(cls, V: StencilVectorSpace, M: Sequence, K: Sequence, mass_coef: float = 1.0, dirichlet=None):
+        """-Δu + c u in Kronecker-sum form from per-axis 1D (mass, stiffness) bands.
+        ``dirichlet``: constrained faces (:func:`poms_amd.boundary.normalize_faces`); the
+        factors of a constrained axis go through :func:`~poms_amd.splines.constrain_1d`,
+        so the free rows are those of ``Π A Π`` and the constrained rows decouple from
+        them (into an SPD block that is not diagonal)."""
+        from .boundary import normalize_faces
+        from .splines import constrain_1d
         nd = V.ndim
         M = [_band_of(m) for m in M]
         K = [_band_of(k) for k in K]
         if len(M) != nd or len(K) != nd:
             raise ValueError("need one (M, K) pair per axis")
+        faces = normalize_faces(dirichlet, nd)
+        if faces is not None:
+            if V.is_distributed or V.is_cart:
+                raise NotImplementedError("dirichlet: distributed (slab / Cart) spaces are not supported")
+            M = [constrain_1d(m, lo, hi) for m, (lo, hi) in zip(M, faces)]
+            K = [constrain_1d(k, lo, hi) for k, (lo, hi) in zip(K, faces)]
         for d in range(nd):
             if M[d].shape[0] != V.npts[d] or K[d].shape != M[d].shape:
                 raise ValueError(f"axis {d}: factor rows do not match npts")
@@ -616,6 +660,7 @@ class KronOperator:
             bands = {"A1": _unit_band(pmax, c), "B1": _unit_band(pmax, 1.0), "M2": Mw[0], "K2": Kw[0]}
         op = cls(V, "sum", bands, pmax)
         op.M, op.K, op.mass_coef = M, K, c
+        op._dirichlet = faces
         return op
 
     @classmethod
@@ -1130,6 +1175,8 @@ class StencilMatrix(KronOperator):
                   g0, n0g, C.byref(h))
         self._hh = h
         self._dirty = False
+        if self._dirichlet is not None:   # (a new handle starts unconstrained)
+            self._push_dirichlet(h, self._dirichlet)
 
     def __del__(self):
         h = getattr(self, "_hh", None)
@@ -1206,7 +1253,13 @@ class StencilMatrix(KronOperator):
             cols.append(np.ravel_multi_index(tgt[ok].T, V.npts))
             vals.append(flat[ok, kk])
         n = V.dimension
-        return sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n))
+        A = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n))
+        if self._dirichlet is not None:   # the matrix `dot` applies: Π A Π + (I − Π) diag(A) (I − Π)
+            from .boundary import constrained_mask
+            fixed = constrained_mask(V.npts, self._dirichlet).reshape(-1)
+            free = sp.diags((~fixed).astype(np.float64))
+            A = (free @ A @ free + sp.diags(np.where(fixed, A.diagonal(), 0.0))).tocsr()
+        return A
 
     def tocsr(self):
         return self.tosparse()
