@@ -33,9 +33,10 @@
 extern "C" {
 #endif
 
-#define POMS_ABI_VERSION 8 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
+#define POMS_ABI_VERSION 9 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
                             * 7: poms_pcg_opts.n_pbuf, .pbuf;
-                            * 8: poms_op_set_dirichlet, poms_op_get_dirichlet */
+                            * 8: poms_op_set_dirichlet, poms_op_get_dirichlet;
+                            * 9: poms_op_cheby_step, poms_op_cheby_supported */
 
 /* operator forms (see poms_op_create) */
 #define POMS_FORM_SINGLE 0 /* y = F0 (x) F1 (x) F2 x                                  */
@@ -337,6 +338,20 @@ int poms_op_sweep2_supported(poms_op* op, int* yes);
  * the two-sweep launches (POMS_J2FZ=0: off).                                      */
 int poms_op_jacobi3_from_zero(poms_op* op, double omega, const double* b, double* x_out, double* norms_out,
                               void* stream);
+/* One step of the three-term Chebyshev-Jacobi recurrence in one launch,
+ *     y <- x + beta (x - y) + alpha (b - A x) / diag(A)      (interior entries),
+ * with A as every launch applies it (Dirichlet faces included): y holds x_{k-1} on entry
+ * and x_{k+1} on exit, each entry read and written by its one owner thread.  With
+ * beta == 0 the old y is not read (the first step may take an uninitialised buffer).
+ * No reductions, no allocation, no synchronisation: a smoothing call is a fixed chain of
+ * these launches and can be captured.  General-stencil and matrix-free operators
+ * (poms_op_cheby_supported); refused: null pointers, y aliasing x or b, the Kronecker
+ * forms (compose poms_op_jacobi_sweep and poms_vec_axpby), slabs and Cart blocks.
+ * Replaces: the smoothing calls `pcg(Af, damped_jacobi, bf, ...)` of the reference's
+ * cycle, `sources/mg_jac.py:88,104`, by a polynomial in D^-1 A without inner products. */
+int poms_op_cheby_step(poms_op* op, double alpha, double beta, const double* b,
+                       const double* x, double* y, int64_t z_begin, int64_t z_end, void* stream);
+int poms_op_cheby_supported(poms_op* op, int* yes);
 /* x = scale * b / diag(A) on the interior.  With scale = 1 this is
  * `jacobi(A, b)` (`sources/solvers.py:139-163`); with scale = omega it is the
  * first damped-Jacobi sweep from x0 = 0 (A.0 = 0 exactly).                    */

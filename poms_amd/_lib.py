@@ -125,6 +125,8 @@ _SIGS = {
     "poms_op_jacobi_sweep": [_vp, _d, _vp, _vp, _vp, _i64, _i64, _i, _vp],
     "poms_op_jacobi_sweep_dot": [_vp, _d, _vp, _vp, _vp, _i64, _i64, _i, _vp],
     "poms_op_fused_dot_supported": [_vp, C.POINTER(_i)],
+    "poms_op_cheby_step": [_vp, _d, _d, _vp, _vp, _vp, _i64, _i64, _vp],
+    "poms_op_cheby_supported": [_vp, C.POINTER(_i)],
     "poms_op_jacobi_from_zero": [_vp, _d, _vp, _vp, _i64, _i64, _i, _vp],
     "poms_op_from_zero_supported": [_vp, C.POINTER(_i)],
     "poms_op_sweep2_supported": [_vp, C.POINTER(_i)],

@@ -951,7 +951,7 @@ static bool fused_dot_ok(const poms_op* o) {
 // General-stencil launch (FORM_STENCIL): the epilogues of op_run plus EPI_DIAG.
 static int stencil_run(poms_op* o, int epi, double omega, const double* x, double* y, const double* b,
                        int64_t zb, int64_t ze, int want_norm, void* stream, int want_dot, int64_t zb2,
-                       int64_t ze2, PartRoute* route = nullptr) {
+                       int64_t ze2, PartRoute* route = nullptr, double beta = 0.0) {
     if (route) route->used = false;   // (its own partials layout: the scratch only)
     if (epi == EPI_JACOBI0) { set_error("general stencil: no two-sweeps-from-zero epilogue"); return 1; }
     if (want_dot && epi != EPI_JACOBI && epi != EPI_APPLYDOT) { set_error("general stencil: dot needs Jacobi / apply+dot"); return 1; }
@@ -966,7 +966,7 @@ static int stencil_run(poms_op* o, int epi, double omega, const double* x, doubl
     const bool red = want_norm || want_dot || epi == EPI_APPLYDOT;
     if (stencil_launch(epi, g, o->coef, x, y, b, omega, want_norm ? scr : nullptr,
                        (want_dot || epi == EPI_APPLYDOT) ? scr + std::min<int64_t>(maxb, std::max<int64_t>(1, ((int64_t)(ze - zb + ze2 - zb2) * r.n1 * r.n2 + 255) / 256)) : nullptr,
-                       maxb, as_stream(stream), &nb))
+                       maxb, as_stream(stream), &nb, beta))
         return 1;
     POMS_HIP_CHECK(hipGetLastError());
     o->last_partials = red ? nb : 0;
@@ -979,7 +979,7 @@ static int stencil_run(poms_op* o, int epi, double omega, const double* x, doubl
 // allocated or synchronised here.
 static int matfree_run(poms_op* o, int epi, double omega, const double* x, double* y, const double* b,
                        int64_t zb, int64_t ze, int want_norm, void* stream, int want_dot, int64_t zb2,
-                       int64_t ze2, PartRoute* route = nullptr) {
+                       int64_t ze2, PartRoute* route = nullptr, double beta = 0.0) {
     if (route) route->used = false;   // (stencil_run's layout: the scratch only)
     if (epi == EPI_JACOBI0) { set_error("matrix-free operator: no two-sweeps-from-zero epilogue"); return 1; }
     if (want_dot && epi != EPI_JACOBI && epi != EPI_APPLYDOT) { set_error("matrix-free operator: dot needs Jacobi / apply+dot"); return 1; }
@@ -998,13 +998,13 @@ static int matfree_run(poms_op* o, int epi, double omega, const double* x, doubl
         o->last_partials = want_norm ? nb : 0;
         return 0;
     }
-    if ((epi == EPI_JACOBI || epi == EPI_APPLYDOT) && x == y) { set_error("matrix-free operator: y must not alias x"); return 1; }
+    if ((epi == EPI_JACOBI || epi == EPI_APPLYDOT || epi == EPI_CHEBY) && x == y) { set_error("matrix-free operator: y must not alias x"); return 1; }
     const MatfreeGeom& g = o->mf_geom;
     const int nblk = (int)std::min<int64_t>(g.ntiles, maxb);
     const bool wd = want_dot || epi == EPI_APPLYDOT;
     if (matfree_launch(epi, g, o->mf_ax, x, y, b, o->mf_a, o->mf_c, o->mf_diag, o->mf_mass, omega,
                        want_norm ? scr : nullptr, wd ? scr + nblk : nullptr, maxb, as_stream(stream), &nb,
-                       o->mf_tensor))
+                       o->mf_tensor, beta))
         return 1;
     POMS_HIP_CHECK(hipGetLastError());
     o->last_partials = (want_norm || wd) ? nb : 0;
@@ -1126,15 +1126,16 @@ static int op_run_j2(poms_op* o, int epi, double omega, const double* x, double*
 
 static int op_run(poms_op* o, int epi, double omega, const double* x, double* y, const double* b,
                   int64_t zb, int64_t ze, int want_norm, void* stream, int want_dot = 0,
-                  int64_t zb2 = 0, int64_t ze2 = 0, PartRoute* route = nullptr) {
+                  int64_t zb2 = 0, int64_t ze2 = 0, PartRoute* route = nullptr, double beta = 0.0) {
     if (!o || !x || !y) { set_error("null operator or vector"); return 1; }
     if (epi != EPI_APPLY && !b) { set_error("null right-hand side"); return 1; }
     if (epi == EPI_JACOBI2 || epi == EPI_JACOBI3Z)
         return op_run_j2(o, epi, omega, x, y, b, want_norm, want_dot, stream, route);
     if (o->form == FORM_STENCIL)
-        return stencil_run(o, epi, omega, x, y, b, zb, ze, want_norm, stream, want_dot, zb2, ze2, route);
+        return stencil_run(o, epi, omega, x, y, b, zb, ze, want_norm, stream, want_dot, zb2, ze2, route, beta);
     if (o->form == FORM_MATFREE)
-        return matfree_run(o, epi, omega, x, y, b, zb, ze, want_norm, stream, want_dot, zb2, ze2, route);
+        return matfree_run(o, epi, omega, x, y, b, zb, ze, want_norm, stream, want_dot, zb2, ze2, route, beta);
+    if (epi == EPI_CHEBY) { set_error("Chebyshev step: general-stencil and matrix-free operators only"); return 1; }
     if (epi == EPI_APPLYDOT && !(o->variant == 4 || o->variant == 8 || o->variant == 9 || o->variant == 10)) {
         set_error("apply + x.y: kernel variants 4, 8, 9, 10 only");
         return 1;
@@ -1237,6 +1238,31 @@ int poms_op_jacobi_sweep_dot(poms_op* op, double omega, const double* b, const d
 int poms_op_apply_dot(poms_op* op, const double* x, double* y, int64_t zb, int64_t ze, void* stream) {
     if (x == y) { set_error("apply: y must not alias x"); return 1; }
     return op_run(op, EPI_APPLYDOT, 0.0, x, y, x, zb, ze, 0, stream, 1);
+}
+
+// the forms and layouts whose Chebyshev step is one launch: the general forms, undistributed
+static bool cheby_ok(const poms_op* o) {
+    return general_form(o) && o->g0 == 0 && !(o->ndim == 3 && o->L.n[0] != o->n0g) &&
+           !(o->L.flags & POMS_LAYOUT_GHOST_DATA);
+}
+
+int poms_op_cheby_step(poms_op* op, double alpha, double beta, const double* b, const double* x, double* y,
+                       int64_t zb, int64_t ze, void* stream) {
+    const std::string fn = "poms_op_cheby_step: ";
+    if (!op || !b || !x || !y) { set_error(fn + "null argument"); return 1; }
+    if (y == x || y == b) { set_error(fn + "y must not alias x or b"); return 1; }
+    if (!general_form(op)) {
+        set_error(fn + "Kronecker forms have no fused step (compose poms_op_jacobi_sweep and poms_vec_axpby)");
+        return 1;
+    }
+    if (!cheby_ok(op)) { set_error(fn + "distributed operators (slabs, Cart blocks) are not supported"); return 1; }
+    return op_run(op, EPI_CHEBY, alpha, x, y, b, zb, ze, 0, stream, 0, 0, 0, nullptr, beta);
+}
+
+int poms_op_cheby_supported(poms_op* op, int* yes) {
+    if (!op || !yes) { set_error("poms_op_cheby_supported: null argument"); return 1; }
+    *yes = cheby_ok(op) ? 1 : 0;
+    return 0;
 }
 
 int poms_op_apply_dot_supported(poms_op* op, int* yes) {

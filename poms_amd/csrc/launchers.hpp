@@ -79,7 +79,7 @@ int assemble_launch(const AssembleAxis* ax, int g0, int nl0, const double* a_q, 
 int stencil_to_spl_launch(const StencilGeom& g, const double* coef, double* out, hipStream_t st);
 int stencil_launch(int epi, const StencilGeom& g, const double* coef, const double* x, double* y,
                    const double* b, double omega, double* partial, double* partial2, int max_blocks,
-                   hipStream_t st, int* nblk_out);
+                   hipStream_t st, int* nblk_out, double beta = 0.0);   // (beta: EPI_CHEBY only)
 
 // ---- matfree.hip ------------------------------------------------------------------
 int matfree_tile();           // output columns per tile edge (axes 1, 2)
@@ -91,7 +91,7 @@ int matfree_diag_launch(const AssembleAxis* ax, const double* a_q, const double*
 int matfree_launch(int epi, const MatfreeGeom& g, const AssembleAxis* ax, const double* x, double* y, const double* b,
                    const double* a_q, const double* c_q, const double* diag, double mass_coef, double omega,
                    double* partial, double* partial2, int max_blocks, hipStream_t st, int* nblk_out,
-                   bool tensor = false);
+                   bool tensor = false, double beta = 0.0);   // (beta: EPI_CHEBY only)
 bool matfree_tensor_builds_ok(std::string* why);   // no scratch, at most 256 registers
 
 // ---- stencil_galerkin.hip ---------------------------------------------------------

@@ -24,7 +24,8 @@
 // functions) are staged in LDS once per tile, so the stages read no table from global
 // memory; a_q and c_q of a wave's next row are fetched a round ahead.
 // An output plane is final when the last element of its support has passed; the
-// epilogue (the general stencil's: apply, residual, Jacobi, apply + dot) runs there.
+// epilogue (the general stencil's: apply, residual, Jacobi, apply + dot, Chebyshev step)
+// runs there.
 // Every output is owned by one thread and summed in a fixed order, there are no
 // atomics, and the per-block partial sums go through the usual reduction: two calls
 // give the same bits.  Only interior entries of y are stored; x is read inside its
@@ -71,7 +72,8 @@ __global__ void __launch_bounds__(256)
 matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1, const AssembleAxis A2,
                const double* __restrict__ x, double* __restrict__ y, const double* __restrict__ b,
                const double* __restrict__ a_q, const double* __restrict__ c_q, const double* __restrict__ diag,
-               double mass_coef, double omega, double* __restrict__ partial, double* __restrict__ partial2) {
+               double mass_coef, double omega, double* __restrict__ partial, double* __restrict__ partial2,
+               double beta) {
     __shared__ double sX[(MF_PMAX + 1) * MF_WW];   // ring of x window planes
     __shared__ double sU[2 * MF_WW];               // B0 x, B0' x
     __shared__ double sT[3 * MF_QW];               // B1 U, B1 U', B1' U  at [q1][c2]
@@ -320,6 +322,13 @@ matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1
                         y[xo] = xn;
                         nrm = fma(dr, dr, nrm);
                         dot = fma(xn, bv, dot);
+                    } else if constexpr (EPI == EPI_CHEBY) {
+                        // the general stencil's Chebyshev step: y holds x_{k-1} on entry, x_{k+1}
+                        // on exit; beta == 0 selects, the old y is then not read
+                        const double xv = x[xo];
+                        const double dr = omega * (b[xo] - s) / diag[((int64_t)jf * g.n1 + i1) * g.n2 + i2];
+                        const double mom = beta != 0.0 ? beta * (xv - y[xo]) : 0.0;
+                        y[xo] = xv + mom + dr;
                     } else {   // EPI_APPLYDOT
                         y[xo] = s;
                         dot = fma(x[xo], s, dot);
@@ -417,12 +426,13 @@ int matfree_diag_launch(const AssembleAxis* ax, const double* a_q, const double*
 // any number of registers up to 256 keeps that, scratch does not.  False, with a
 // message, if a build reports scratch or the attributes cannot be read.
 bool matfree_tensor_builds_ok(std::string* why) {
-    const void* fns[8] = {
+    const void* fns[10] = {
         (const void*)matfree_kernel<EPI_APPLY, true, false>, (const void*)matfree_kernel<EPI_RESID, true, false>,
         (const void*)matfree_kernel<EPI_JACOBI, true, false>, (const void*)matfree_kernel<EPI_APPLYDOT, true, false>,
         (const void*)matfree_kernel<EPI_APPLY, true, true>, (const void*)matfree_kernel<EPI_RESID, true, true>,
-        (const void*)matfree_kernel<EPI_JACOBI, true, true>, (const void*)matfree_kernel<EPI_APPLYDOT, true, true>};
-    for (int k = 0; k < 8; ++k) {
+        (const void*)matfree_kernel<EPI_JACOBI, true, true>, (const void*)matfree_kernel<EPI_APPLYDOT, true, true>,
+        (const void*)matfree_kernel<EPI_CHEBY, true, false>, (const void*)matfree_kernel<EPI_CHEBY, true, true>};
+    for (int k = 0; k < 10; ++k) {
         hipFuncAttributes at{};
         if (hipFuncGetAttributes(&at, fns[k]) != hipSuccess) {
             (void)hipGetLastError();
@@ -442,13 +452,14 @@ bool matfree_tensor_builds_ok(std::string* why) {
 // a workgroup then takes every gridDim-th tile.
 int matfree_launch(int epi, const MatfreeGeom& g, const AssembleAxis* ax, const double* x, double* y, const double* b,
                    const double* a_q, const double* c_q, const double* diag, double mass_coef, double omega,
-                   double* partial, double* partial2, int max_blocks, hipStream_t st, int* nblk_out, bool tensor) {
+                   double* partial, double* partial2, int max_blocks, hipStream_t st, int* nblk_out, bool tensor,
+                   double beta) {
     const int nb = (int)std::min<int64_t>(g.ntiles, max_blocks);
     *nblk_out = nb;
     if (nb <= 0) return 0;
 #define POMS_MF_LAUNCH1(E, T, M)                                                                              \
     hipLaunchKernelGGL((matfree_kernel<E, T, M>), dim3(nb), dim3(256), 0, st, g, ax[0], ax[1], ax[2], x, y, b, a_q,  \
-                       c_q, diag, mass_coef, omega, partial, partial2)
+                       c_q, diag, mass_coef, omega, partial, partial2, beta)
 #define POMS_MF_LAUNCH(E)                                                                                     \
     do {                                                                                                      \
         if (tensor && g.dmask) POMS_MF_LAUNCH1(E, true, true);                                                \
@@ -461,6 +472,7 @@ int matfree_launch(int epi, const MatfreeGeom& g, const AssembleAxis* ax, const 
         case EPI_RESID: POMS_MF_LAUNCH(EPI_RESID); break;
         case EPI_JACOBI: POMS_MF_LAUNCH(EPI_JACOBI); break;
         case EPI_APPLYDOT: POMS_MF_LAUNCH(EPI_APPLYDOT); break;
+        case EPI_CHEBY: POMS_MF_LAUNCH(EPI_CHEBY); break;
         default:
             set_error("matrix-free operator: unsupported epilogue");
             return 1;

@@ -23,7 +23,7 @@ template <int EPI>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96)))
 stencil_kernel(const StencilGeom g, const double* __restrict__ coef, const double* __restrict__ x,
                double* __restrict__ y, const double* __restrict__ b, double omega,
-               double* __restrict__ partial, double* __restrict__ partial2) {
+               double* __restrict__ partial, double* __restrict__ partial2, double beta) {
     __shared__ double red[4];
     const int64_t npl = (int64_t)g.n1 * g.n2;
     const int64_t nr1 = (int64_t)(g.z_end - g.z_begin) * npl;
@@ -102,6 +102,14 @@ stencil_kernel(const StencilGeom g, const double* __restrict__ coef, const doubl
             y[xo] = xn;
             nrm = fma(dr, dr, nrm);
             dot = fma(xn, bv, dot);
+        } else if constexpr (EPI == EPI_CHEBY) {
+            // one step of the three-term Chebyshev recurrence: y holds x_{k-1} on entry and
+            // x_{k+1} on exit, each entry read and written by this thread alone.  beta == 0
+            // (the first step) selects: the old y may be uninitialised and is not read.
+            const double xv = x[xo];
+            const double dr = omega * (b[xo] - s) / coef[kc * g.cstride + lin];
+            const double mom = beta != 0.0 ? beta * (xv - y[xo]) : 0.0;
+            y[xo] = xv + mom + dr;
         } else {   // EPI_APPLYDOT
             y[xo] = s;
             dot = fma(x[xo], s, dot);
@@ -242,7 +250,7 @@ int stencil_to_spl_launch(const StencilGeom& g, const double* coef, double* out,
 // Blocks of the grid-stride launch (<= max_blocks so the partials fit the scratch).
 int stencil_launch(int epi, const StencilGeom& g, const double* coef, const double* x, double* y,
                    const double* b, double omega, double* partial, double* partial2, int max_blocks,
-                   hipStream_t st, int* nblk_out) {
+                   hipStream_t st, int* nblk_out, double beta) {
     const int64_t total = (int64_t)((g.z_end - g.z_begin) + (g.z2_end - g.z2_begin)) * g.n1 * g.n2;
     const int64_t want = (total + 255) / 256;
     const int nb = (int)std::min<int64_t>(std::max<int64_t>(want, 1), max_blocks);
@@ -251,23 +259,27 @@ int stencil_launch(int epi, const StencilGeom& g, const double* coef, const doub
     switch (epi) {
         case EPI_APPLY:
             hipLaunchKernelGGL(stencil_kernel<EPI_APPLY>, dim3(nb), dim3(256), 0, st, g, coef, x, y, b, omega,
-                               partial, partial2);
+                               partial, partial2, beta);
             break;
         case EPI_RESID:
             hipLaunchKernelGGL(stencil_kernel<EPI_RESID>, dim3(nb), dim3(256), 0, st, g, coef, x, y, b, omega,
-                               partial, partial2);
+                               partial, partial2, beta);
             break;
         case EPI_JACOBI:
             hipLaunchKernelGGL(stencil_kernel<EPI_JACOBI>, dim3(nb), dim3(256), 0, st, g, coef, x, y, b, omega,
-                               partial, partial2);
+                               partial, partial2, beta);
             break;
         case EPI_APPLYDOT:
             hipLaunchKernelGGL(stencil_kernel<EPI_APPLYDOT>, dim3(nb), dim3(256), 0, st, g, coef, x, y, b, omega,
-                               partial, partial2);
+                               partial, partial2, beta);
             break;
         case EPI_DIAG:
             hipLaunchKernelGGL(stencil_kernel<EPI_DIAG>, dim3(nb), dim3(256), 0, st, g, coef, x, y, b, omega,
-                               partial, partial2);
+                               partial, partial2, beta);
+            break;
+        case EPI_CHEBY:
+            hipLaunchKernelGGL(stencil_kernel<EPI_CHEBY>, dim3(nb), dim3(256), 0, st, g, coef, x, y, b, omega,
+                               partial, partial2, beta);
             break;
         default:
             set_error("general stencil: unsupported epilogue");

@@ -175,11 +175,11 @@ class MatrixFreeVCycle(GalerkinVCycle):
     ``l``; ``A1``: the level-1 :class:`~poms_amd.stencil.StencilMatrix` (on the space
     of ``P[0]``'s columns)."""
 
-    def __init__(self, A: MatrixFreeOperator, P, A1, *, tol: float = 1e-6, maxiters=None):
+    def __init__(self, A: MatrixFreeOperator, P, A1, *, tol: float = 1e-6, maxiters=None, **smoother_kw):
         if tuple(A1.space.npts) != tuple(np.shape(p)[1] for p in P[0]):
             raise ValueError("the level-1 operator does not live on the columns of P[0]")
         self._A1 = A1
-        super().__init__(A, P, tol=tol, maxiters=maxiters)
+        super().__init__(A, P, tol=tol, maxiters=maxiters, **smoother_kw)
 
     def _coarse_op(self, l: int):
         return self._A1 if l == 0 else super()._coarse_op(l)
@@ -187,12 +187,13 @@ class MatrixFreeVCycle(GalerkinVCycle):
     @classmethod
     def uniform(cls, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *, a=None, c=None,
                 mass_coef: float = 1.0, nquad: int | None = None, device=None, tol: float = 1e-6, maxiters=None,
-                mapping=None, dirichlet=None):
+                mapping=None, dirichlet=None, **smoother_kw):
         """Dyadic uniform hierarchy, as :meth:`GalerkinVCycle.uniform`.  ``a`` / ``c``:
         None, scalars or callables (they are sampled on two quadrature grids, the
         finest level's and level 1's).  ``mapping``: the operator of the mapped domain
         (:mod:`poms_amd.geometry`), its tensor sampled on those two grids; ``a`` / ``c``
-        are then functions of the physical coordinates."""
+        are then functions of the physical coordinates.  ``smoother_kw``: ``smoother``,
+        ``cheby_degree``, ``cheby_ratio``, ``cheby_safety`` of :class:`~poms_amd.mg.GalerkinVCycle`."""
         for f in (a, c):
             if f is not None and not callable(f) and np.ndim(f) != 0:
                 raise ValueError("a / c must be None, scalars or callables here: they are sampled on two grids")
@@ -205,6 +206,6 @@ class MatrixFreeVCycle(GalerkinVCycle):
         A = MatrixFreeOperator(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef, nquad=nquad, dirichlet=dirichlet)
         V1 = StencilVectorSpace([len(knots[1]) - p - 1] * ndim, [p] * ndim, device=V.device, align=True)
         A1 = assemble_stencil(V1, [knots[1]] * ndim, a=a1, c=c1, mass_coef=mass_coef, nquad=nquad)
-        mg = cls(A, [[P1l] * ndim for P1l in P1], A1, tol=tol, maxiters=maxiters)
+        mg = cls(A, [[P1l] * ndim for P1l in P1], A1, tol=tol, maxiters=maxiters, **smoother_kw)
         mg.p, mg.ndim, mg.cells, mg.knots, mg.P1 = int(p), int(ndim), cells, knots, P1
         return mg

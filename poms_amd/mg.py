@@ -41,7 +41,8 @@ from . import _lib
 from . import runtime as rt
 from .boundary import check_unit_rows, constrain_dense, constrain_prolongation, normalize_faces
 from .multilevels import KronTransfer, knots_to_insert
-from .solvers import damped_jacobi, defer_x_count, pcg, pcg_kron
+from .solvers import (_cached_lmax, chebyshev, chebyshev_work, damped_jacobi, defer_x_count, pcg,
+                      pcg_kron)
 from .splines import (array_to_mat_stencil, assemble_1d, band_to_dense, collocation_cardinal_splines,
                       matrix_multi_stages, uniform_knots)
 from .stencil import F64, KronOperator, StencilVector, StencilVectorSpace
@@ -123,13 +124,52 @@ def _smoother_counts(maxiters, nlevels: int) -> list:
     return out
 
 
+def _check_smoother(smoother: str, dist=None, post_smoother: str = "jacobi") -> str:
+    """The smoother's name, after the combinations the Chebyshev smoother does not implement."""
+    if smoother not in ("jacobi", "chebyshev"):
+        raise ValueError("smoother must be 'jacobi' (pcg with damped Jacobi, mg_jac.py) or 'chebyshev'")
+    if smoother == "chebyshev" and dist is not None:
+        raise ValueError("smoother='chebyshev': distributed (slab / Cart) V-cycles are not supported")
+    if smoother == "chebyshev" and post_smoother == "glt":
+        raise ValueError("smoother='chebyshev': the GLT post-smoother is not supported")
+    return smoother
+
+
 class _VCycle:
     """What the V-cycles share: the sequence of one level, the right-hand side of ones and
     the dense solve on the coarsest level.  A constructor sets ``tol`` and, per level with
     a coarser one below it, ``ops``, ``spaces``, ``transfers``, ``fused`` (residual ->
-    restriction in one pass) and ``maxiters``, then calls :meth:`_set_coarse`."""
+    restriction in one pass) and ``maxiters``, then calls :meth:`_set_coarse` and, for a
+    smoother other than the default, :meth:`_set_smoother`.
+
+    ``smoother="chebyshev"`` replaces both ``pcg(A_l, damped_jacobi, b_l)`` calls of a level
+    by :func:`~poms_amd.solvers.chebyshev` of degree ``cheby_degree`` (an int, or one per
+    level) over ``[cheby_safety lmax / cheby_ratio, cheby_safety lmax]``, lmax(D^-1 A_l)
+    estimated once at construction.  The same polynomial runs before and after the coarse
+    correction and there are no stop tests, so the cycle from zero is a fixed symmetric
+    linear operator: :meth:`preconditioner` hands it to ``solvers.pcg``."""
 
     glt = None   # level 0's post-smoother factors where it is pcg_kron (TwoLevelVCycle)
+    smoother = "jacobi"
+
+    def _set_smoother(self, smoother: str, cheby_degree=10, cheby_ratio: float = 30.0,
+                      cheby_safety: float = 1.1) -> None:
+        self.smoother = smoother
+        if smoother != "chebyshev":
+            return
+        L = len(self.transfers)
+        degs = [int(cheby_degree)] * L if np.ndim(cheby_degree) == 0 else [int(d) for d in cheby_degree]
+        if len(degs) != L or min(degs) < 1:
+            raise ValueError(f"cheby_degree needs one integer >= 1, or {L} of them")
+        self.cheby_degrees, self.cheby_ratio, self.cheby_safety = degs, float(cheby_ratio), float(cheby_safety)
+        self.cheby_lmax = [_cached_lmax(A) for A in self.ops[:L]]
+        self._cheby_work = [chebyshev_work(A) for A in self.ops[:L]]
+
+    def preconditioner(self):
+        """``psolve`` for :func:`~poms_amd.solvers.pcg`: one cycle from zero on ``r``.  A
+        legitimate CG preconditioner with ``smoother="chebyshev"`` only (a pcg-smoothed
+        cycle is not a fixed linear operator)."""
+        return lambda A, r: self.cycle(r)[0]
 
     def _set_coarse(self, Ac: np.ndarray) -> None:
         """The coarsest level from its dense operator: the inverse (the reference's
@@ -174,10 +214,16 @@ class _VCycle:
 
     def _level(self, l: int, b: StencilVector, x0: StencilVector | None) -> StencilVector:
         A, tr, n = self.ops[l], self.transfers[l], self.maxiters[l]
-        # (_skip_tail: a smoother call's last iteration ends at x and r.r, see solvers.pcg)
-        # (_defer_x: x brought up to date once per call where that pays, see solvers.defer_x_count)
-        dx = defer_x_count(A, self.spaces[l], n)
-        x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=n, _skip_tail=True, _defer_x=dx)
+        cheby = self.smoother == "chebyshev"
+        if cheby:
+            ckw = dict(degree=self.cheby_degrees[l], lmax=self.cheby_lmax[l], ratio=self.cheby_ratio,
+                       safety=self.cheby_safety, work=self._cheby_work[l])
+            x, ipre = chebyshev(A, b, x0=x0, **ckw)
+        else:
+            # (_skip_tail: a smoother call's last iteration ends at x and r.r, see solvers.pcg)
+            # (_defer_x: x brought up to date once per call where that pays, see solvers.defer_x_count)
+            dx = defer_x_count(A, self.spaces[l], n)
+            x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=n, _skip_tail=True, _defer_x=dx)
         if self.fused[l]:
             rc = tr.resid_restrict(A, b, x, out=self.rcs[l])
         else:
@@ -194,7 +240,13 @@ class _VCycle:
             ec = Vc.interior(ecv._data).contiguous().view(-1)
         tr.prolong_add(ec, x)
         x.update_ghost_regions()
-        if l == 0 and self.glt is not None:
+        if cheby:
+            # (the same polynomial as before the correction, continued in the level's buffers;
+            # level 0's result leaves them, so that the caller owns what it gets)
+            x, ipos = chebyshev(A, b, x0=x, _x0_owned=True, **ckw)
+            if l == 0:
+                x = x.copy()
+        elif l == 0 and self.glt is not None:
             x, ipos = pcg_kron(A, self.glt, b, x0=x, tol=self.tol, maxiter=self.p + 1, _skip_tail=True)
         else:
             # (x is this cycle's own temporary, never the caller's x0: iterate in its buffer, no copy)
@@ -218,10 +270,12 @@ class TwoLevelVCycle(_VCycle):
     def __init__(self, p: int, ncells_fine: int, ncells_coarse: int = 8, ndim: int = 3, *,
                  dist=None, mass_coef: float = 1.0, device=None, knots_fine=None, knots_coarse=None,
                  tol: float = 1e-6, maxiter: int = 10, chunk: int = 0, align: bool = True,
-                 post_smoother: str = "jacobi", fused_restrict: bool | None = None, dirichlet=None):
+                 post_smoother: str = "jacobi", fused_restrict: bool | None = None, dirichlet=None,
+                 smoother: str = "jacobi", cheby_degree=10, cheby_ratio: float = 30.0, cheby_safety: float = 1.1):
         self.p, self.ndim = int(p), int(ndim)
         if post_smoother not in ("jacobi", "glt"):
             raise ValueError("post_smoother must be 'jacobi' (mg_jac.py) or 'glt' (mg_glt.py)")
+        _check_smoother(smoother, dist, post_smoother)
         self.post_smoother = post_smoother
         # Dirichlet faces: constrained 1D factors on both levels, transfers from P Π_c, and
         # the coarse factors constrain(P^T F P) (not (PΠ)^T F~ (PΠ), which is singular)
@@ -257,6 +311,7 @@ class TwoLevelVCycle(_VCycle):
         if post_smoother == "glt":
             Cm = array_to_mat_stencil(n, p, collocation_cardinal_splines(p, n))
             self.glt = [Cm] * ndim
+        self._set_smoother(smoother, cheby_degree, cheby_ratio, cheby_safety)
 
     # the one level's entries of the base's lists, under the names of `sources/mg_jac.py`
     transfer = property(lambda self: self.transfers[0])
@@ -290,7 +345,9 @@ class MultilevelVCycle(_VCycle):
 
     def __init__(self, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *,
                  dist=None, mass_coef: float = 1.0, device=None, tol: float = 1e-6, maxiters=None,
-                 align: bool = True, chunk: int = 0, fused_restrict: bool | None = None, dirichlet=None):
+                 align: bool = True, chunk: int = 0, fused_restrict: bool | None = None, dirichlet=None,
+                 smoother: str = "jacobi", cheby_degree=10, cheby_ratio: float = 30.0, cheby_safety: float = 1.1):
+        _check_smoother(smoother, dist)
         self.cells = cells = dyadic_cells(ncells_fine, ncells_coarsest)
         self.dirichlet = faces = _kron_dirichlet(dirichlet, ndim, dist)   # (as TwoLevelVCycle)
         self.p, self.ndim, self.tol = int(p), int(ndim), tol
@@ -321,6 +378,7 @@ class MultilevelVCycle(_VCycle):
             Mc = [constrain_dense(m, m.shape[:1], [f]) for m, f in zip(Mc, faces)]
             Kc = [constrain_dense(k, k.shape[:1], [f]) for k, f in zip(Kc, faces)]
         self._set_coarse(galerkin_coarse_dense(Mc, Kc, ndim, mass_coef))
+        self._set_smoother(smoother, cheby_degree, cheby_ratio, cheby_safety)
 
 
 class GalerkinVCycle(_VCycle):
@@ -343,9 +401,11 @@ class GalerkinVCycle(_VCycle):
     (checked), ``Π_c (PᵀAP) Π_c = (PΠ_c)ᵀ (Π_f A Π_f) (PΠ_c)``.
     """
 
-    def __init__(self, A, P, *, tol: float = 1e-6, maxiters=None):
+    def __init__(self, A, P, *, tol: float = 1e-6, maxiters=None, smoother: str = "jacobi", cheby_degree=10,
+                 cheby_ratio: float = 30.0, cheby_safety: float = 1.1):
         if len(P) < 1:
             raise ValueError("the hierarchy needs at least two levels")
+        _check_smoother(smoother)
         self.tol = tol
         self.maxiters = _smoother_counts(maxiters, len(P) + 1)
         self.P = [[np.ascontiguousarray(p, dtype=np.float64) for p in Pl] for Pl in P]
@@ -362,6 +422,7 @@ class GalerkinVCycle(_VCycle):
         self.fused = [False] * len(P)
         # coarsest level: its Galerkin operator, inverted densely
         self._set_coarse(self.ops[-1].toarray())
+        self._set_smoother(smoother, cheby_degree, cheby_ratio, cheby_safety)
 
     def _coarse_op(self, l: int):
         """Level ``l+1``'s operator from level ``l``'s (subclasses may rediscretise)."""
@@ -371,20 +432,22 @@ class GalerkinVCycle(_VCycle):
     @classmethod
     def uniform(cls, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *, a=None, c=None,
                 mass_coef: float = 1.0, device=None, tol: float = 1e-6, maxiters=None, mapping=None,
-                dirichlet=None):
+                dirichlet=None, **smoother_kw):
         """Dyadic uniform hierarchy (as :class:`MultilevelVCycle`'s) under
         ``-∇·(a∇u) + c u`` assembled on the finest knots by
         :func:`~poms_amd.assembly.assemble_stencil`.  ``mapping`` (a
         :class:`~poms_amd.geometry.Mapping` or ``SplineMapping``): the operator of the
         mapped domain, its tensor sampled on the finest quadrature grid (``a`` / ``c``
-        are then functions of the physical coordinates)."""
+        are then functions of the physical coordinates).  ``smoother_kw``: ``smoother``,
+        ``cheby_degree``, ``cheby_ratio``, ``cheby_safety`` of the constructor."""
         from .assembly import assemble_stencil, axis_tables
+        _check_smoother(smoother_kw.get("smoother", "jacobi"))
         cells, knots, P1, V = uniform_hierarchy(p, ncells_fine, ncells_coarsest, ndim, device)
         if mapping is not None:
             pts = axis_tables(knots[0], p)["points"].reshape(-1)
             a, c, _ = mapping.pullback([pts] * ndim, a=a, c=c, mass_coef=mass_coef, device=f"cuda:{V.device}")
         A = assemble_stencil(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef, dirichlet=dirichlet)
-        mg = cls(A, [[P1l] * ndim for P1l in P1], tol=tol, maxiters=maxiters)
+        mg = cls(A, [[P1l] * ndim for P1l in P1], tol=tol, maxiters=maxiters, **smoother_kw)
         mg.p, mg.ndim, mg.cells, mg.knots, mg.P1 = int(p), int(ndim), cells, knots, P1
         return mg
 

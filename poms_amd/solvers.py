@@ -556,3 +556,155 @@ def crl(A, b, x0=None, tol=1e-5, maxiter=1000, verbose=False):
         print("+---------+---------------------+")
     info = {"niter": k, "success": sr < tol_sqr, "res_norm": sqrt(sr)}
     return x, info
+
+
+# ---- Chebyshev-Jacobi: a polynomial smoother without inner products ------------------
+# Replaces the smoothing calls `pcg(Af, damped_jacobi, bf, ...)` of the reference's cycle
+# (`sources/mg_jac.py:88,104`) where D^-1 A has eigenvalues beyond 2/omega = 3 (B-splines
+# at p = 3 in 2D, from p = 2 in 3D) and plain damped Jacobi is no contraction.
+
+def chebyshev_coefficients(lmin, lmax, degree):
+    """``(alpha, beta)``, two lists of ``degree`` floats, of the three-term recurrence
+
+        x_{k+1} = x_k + beta_k (x_k - x_{k-1}) + alpha_k D^-1 (b - A x_k),  k = 0 .. degree-1
+
+    whose error polynomial is the Chebyshev polynomial of [lmin, lmax] scaled to 1 at 0:
+    on a scalar operator lam with b = 0, x_0 = 1 it gives
+    ``x_k = T_k((theta - lam)/delta) / T_k(sigma)``.  theta = (lmax + lmin)/2,
+    delta = (lmax - lmin)/2, sigma = theta/delta; alpha_0 = 1/theta, beta_0 = 0,
+    rho_0 = 1/sigma; rho_k = 1/(2 sigma - rho_{k-1}), alpha_k = 2 rho_k/delta,
+    beta_k = rho_k rho_{k-1}."""
+    lmin, lmax = float(lmin), float(lmax)
+    if not (0.0 < lmin < lmax):
+        raise ValueError(f"chebyshev_coefficients: need 0 < lmin < lmax, got [{lmin}, {lmax}]")
+    if int(degree) != degree or degree < 1:
+        raise ValueError(f"chebyshev_coefficients: degree must be an integer >= 1, got {degree}")
+    theta, delta = (lmax + lmin) / 2.0, (lmax - lmin) / 2.0
+    sigma = theta / delta
+    alpha, beta, rho = [1.0 / theta], [0.0], 1.0 / sigma
+    for _ in range(1, int(degree)):
+        rho_new = 1.0 / (2.0 * sigma - rho)
+        alpha.append(2.0 * rho_new / delta)
+        beta.append(rho_new * rho)
+        rho = rho_new
+    return alpha, beta
+
+
+def estimate_lmax(A, iters=10, seed=0):
+    """The largest Ritz value of ``iters`` Lanczos steps for ``A v = lambda D v``,
+    D = diag(A): an estimate of lambda_max(D^-1 A) from below (never above it in exact
+    arithmetic; within 1.5 % after 10 steps on the B-spline operators of DESIGN §3.17).
+
+    The start vector is ``np.random.default_rng(seed).standard_normal(n)`` over the
+    interior in C order.  The steps run ``A.dot``, ``diag_scale``, ``dot`` and ``axpby_``
+    on the device; the coefficients are read on the host every step (a set-up path) and
+    the small tridiagonal matrix is solved there."""
+    import numpy as np
+    import torch
+    if not isinstance(A, KronOperator):
+        raise TypeError("estimate_lmax takes a poms_amd.stencil.KronOperator")
+    if iters < 1:
+        raise ValueError("estimate_lmax: iters must be >= 1")
+    V = A.space
+    z = np.random.default_rng(seed).standard_normal(int(np.prod(V.npts))).reshape(V.npts)
+    v = V.zeros().from_numpy(z)
+    # u = D v: the diagonal from one diag_scale of ones (1/diag), the only elementwise
+    # product of the estimate
+    u, w = V.zeros(), V.empty()
+    V.interior(u._data).fill_(1.0)
+    A.diag_scale(u, w, 1.0)
+    V.interior(u._data).copy_(V.interior(v._data) / V.interior(w._data))
+    u._mark_written()
+    nrm = sqrt(u.dot(v))
+    u *= 1.0 / nrm
+    v *= 1.0 / nrm
+    up, r = V.zeros(), V.empty()
+    al, be, b = [], [], 0.0
+    for j in range(int(iters)):
+        v.update_ghost_regions()
+        A.dot(v, out=r)
+        a = r.dot(v)
+        al.append(a)
+        if j + 1 == iters:
+            break
+        r.axpby_(-a, u, 1.0)             # r = A v - a u - b u_prev  (D-orthogonal to v, v_prev)
+        if b != 0.0:
+            r.axpby_(-b, up, 1.0)
+        A.diag_scale(r, w, 1.0)          # w = D^-1 r
+        b2 = r.dot(w)                    # ||w||_D^2
+        if not b2 > (1e-14 * abs(a)) ** 2:
+            break                        # an invariant subspace: the Ritz values are exact
+        b = sqrt(b2)
+        be.append(b)
+        up, u, r = u, r, up              # u_prev <- u, u <- r / b (r's old buffer is reused)
+        u *= 1.0 / b
+        v.axpby_(1.0 / b, w, 0.0)        # v <- w / b
+    T = np.diag(al) + np.diag(be[:len(al) - 1], 1) + np.diag(be[:len(al) - 1], -1)
+    return float(np.linalg.eigvalsh(T)[-1])
+
+
+def _cached_lmax(A):
+    """``estimate_lmax(A)`` with its defaults, kept on the operator until it changes."""
+    if getattr(A, "_lmax_est", None) is None:
+        A._lmax_est = estimate_lmax(A)
+    return A._lmax_est
+
+
+def chebyshev_work(A):
+    """The buffers one :func:`chebyshev` call on ``A`` ping-pongs: two where the step is
+    one launch, three where it is composed (``A.cheby_supported``)."""
+    return [A.space.empty() for _ in range(2 if A.cheby_supported else 3)]
+
+
+def chebyshev(A, b, x0=None, degree=10, lmax=None, ratio=30.0, safety=1.1, work=None, *, _x0_owned=False):
+    """``degree`` steps of the Chebyshev iteration on D^-1 A over the interval
+    ``[safety lmax / ratio, safety lmax]``; returns ``(x, info)``,
+    ``info = {"niter": degree, "lmin":, "lmax":}`` (the interval).  There is no residual
+    norm and no stop test: the call is a fixed chain of launches -- a fixed polynomial in
+    D^-1 A applied to ``b - A x0``, so a cycle smoothed with it is a fixed linear operator.
+
+    ``lmax=None``: :func:`estimate_lmax`, cached on the operator (dropped when its
+    Dirichlet faces or coefficients change).  ratio 30 and safety 1.1 are the customary
+    defaults of other libraries.  From ``x0=None`` the first step is
+    ``diag_scale(b, x, alpha_0)``.  ``work`` (:func:`chebyshev_work`: vectors of
+    ``V.empty()``, whose ghosts are zero) supplies the buffers, and the call then allocates
+    nothing; the returned ``x`` is one of them (or ``x0``'s buffer with ``_x0_owned``, the
+    V-cycle's own temporaries)."""
+    _check(A, b)
+    V = b.space
+    if lmax is None:
+        lmax = _cached_lmax(A)
+    hi = float(safety) * float(lmax)
+    lo = hi / float(ratio)
+    alpha, beta = chebyshev_coefficients(lo, hi, degree)
+    fused = A.cheby_supported
+    if work is None:
+        work = chebyshev_work(A)
+    if x0 is not None:
+        assert x0.shape == (A.shape[0],)
+    # the buffers free to write: all of work, but for an owned x0 that is one of them (the
+    # V-cycle's post-smoothing continues in the buffers its pre-smoothing ended in)
+    free = [w for w in work if not (_x0_owned and w is x0)]
+    if len(free) < (1 if _x0_owned and x0 is not None else 2) + (0 if fused else 1):
+        raise ValueError(f"chebyshev: work needs {2 if fused else 3} vectors")
+    if any(w is b or w is x0 for w in free):
+        raise ValueError("chebyshev: work must not hold b or x0")
+    t = None if fused else free.pop()
+    if x0 is None:
+        x, y = free[0], free[1]
+        A.diag_scale(b, x, alpha[0])     # x_1 = alpha_0 D^-1 b  (A.0 = 0 exactly)
+        if degree > 1:
+            from . import _lib, runtime as rt
+            import ctypes as C
+            _lib.call("poms_vec_fill", V.ctx, C.byref(V.layout), 0.0, rt.ptr(y._data), rt.stream_handle())   # x_0
+            y._mark_written()
+    else:
+        xin, y = (x0, free[0]) if _x0_owned else (free[1].assign(x0), free[0])
+        xin.update_ghost_regions()
+        A.cheby_step(b, xin, y, alpha[0], 0.0, work=t)
+        x, y = y, xin
+    for k in range(1, int(degree)):
+        x.update_ghost_regions()
+        A.cheby_step(b, x, y, alpha[k], beta[k], work=t)
+        x, y = y, x
+    return x, {"niter": int(degree), "lmin": lo, "lmax": hi}

@@ -543,6 +543,7 @@ class KronOperator:
         self._calls = 0    # operator calls (one call = 1 launch, or 2 when a halo exchange is overlapped)
         self.pads, self.starts, self.ends = V.pads, V.starts, V.ends
         self._dirichlet = None   # constrained faces ((lo, hi) per axis), see poms_amd.boundary
+        self._lmax_est = None    # solvers.estimate_lmax's value (dropped when the operator changes)
 
     # -- Dirichlet faces ---------------------------------------------------------
     @property
@@ -566,6 +567,8 @@ class KronOperator:
         if f is None and self._dirichlet is None:
             return   # (nothing to clear: no handle is made or asked)
         self._push_dirichlet(self._h, f)   # (a refusal leaves the faces as they were)
+        if f != self._dirichlet:
+            self._lmax_est = None
         self._dirichlet = f
 
     def _push_dirichlet(self, h, faces) -> None:
@@ -936,6 +939,47 @@ class KronOperator:
         return V.global_dot(float(nb[0].item()))
 
     @property
+    def cheby_supported(self) -> bool:
+        """The Chebyshev step as one launch (``poms_op_cheby_supported``): the stored
+        stencil and the matrix-free form, undistributed."""
+        v = C.c_int()
+        _lib.call("poms_op_cheby_supported", self._h, C.byref(v))
+        return bool(v.value)
+
+    def cheby_step(self, b: StencilVector, x: StencilVector, y: StencilVector, alpha: float, beta: float,
+                   work: StencilVector | None = None, _composed: bool = False) -> StencilVector:
+        """One step of the three-term Chebyshev-Jacobi recurrence,
+        ``y <- x + beta (x - y) + alpha (b - A x)/diag(A)``: ``y`` holds ``x_{k-1}`` on
+        entry and ``x_{k+1}`` on exit; with ``beta == 0`` its old content is not read.
+
+        One fused launch where :attr:`cheby_supported` (``poms_op_cheby_step``).
+        Elsewhere -- the Kronecker forms -- the step is composed of existing launches and
+        needs one more buffer ``work`` (allocated when None): ``work = jacobi_sweep(b,
+        x, omega=alpha)``, then ``y = (work + beta x) - beta y`` in two ``poms_vec_axpby``.
+        ``_composed`` forces that path (the on-device cross-check of the fused kernel)."""
+        self._check(b, x, y)
+        if y is x or y is b:
+            raise ValueError("y must not alias x or b")
+        V = self.space
+        if not _composed and self.cheby_supported:
+            self._calls += 1
+            _lib.call("poms_op_cheby_step", self._h, float(alpha), float(beta), rt.ptr(b._data), rt.ptr(x._data),
+                      rt.ptr(y._data), 0, V.local_npts[0] if V.ndim == 3 else 1, _stream())
+            y._mark_written()
+            return y
+        if beta == 0.0:
+            self.jacobi_sweep(b, x, y, alpha)
+            return y
+        t = V.empty() if work is None else work
+        self._check(t)
+        if t is x or t is y or t is b:
+            raise ValueError("work must not alias b, x or y")
+        self.jacobi_sweep(b, x, t, alpha)
+        t.axpby_(float(beta), x, 1.0)       # t = x + alpha (b - A x)/diag + beta x
+        y.axpby_(1.0, t, -float(beta))      # y = t - beta y
+        return y
+
+    @property
     def from_zero_supported(self) -> bool:
         V = self.space
         if V.is_distributed and V.is_cart:
@@ -1175,6 +1219,7 @@ class StencilMatrix(KronOperator):
                   g0, n0g, C.byref(h))
         self._hh = h
         self._dirty = False
+        self._lmax_est = None
         if self._dirichlet is not None:   # (a new handle starts unconstrained)
             self._push_dirichlet(h, self._dirichlet)
 
