@@ -287,7 +287,7 @@ int poms_op_apply(poms_op* op, const double* x, double* y, int64_t z_begin,
 /* y = A x, also accumulating x . y per block into scratch[count, 2 count)
  * (count from poms_op_last_partials; reduce with poms_reduce_partials_at).
  * pcg's `q = A.dot(p)` + `p.dot(q)` (`sources/solvers.py:103-104`) in one
- * pass.  Kernel variants 4, 5, 6, 8, 9, 10 (poms_op_apply_dot_supported).    */
+ * pass.  Kernel variants 4, 8, 9, 10 (poms_op_apply_dot_supported).          */
 int poms_op_apply_dot(poms_op* op, const double* x, double* y, int64_t z_begin,
                       int64_t z_end, void* stream);
 int poms_op_apply_dot_supported(poms_op* op, int* yes);
@@ -308,7 +308,7 @@ int poms_op_jacobi_sweep(poms_op* op, double omega, const double* b,
  * scratch[count, 2 count) with count from poms_op_last_partials; reduce them
  * with poms_reduce_partials_at.  With b = r this is pcg's `sr = s.dot(r)`
  * (`sources/solvers.py:91,120`) fused into the last smoothing sweep.
- * Kernel variants 4-10 only (poms_op_fused_dot_supported).                   */
+ * Kernel variants 4, 7, 8, 9, 10 only (poms_op_fused_dot_supported).         */
 int poms_op_jacobi_sweep_dot(poms_op* op, double omega, const double* b,
                              const double* x_in, double* x_out, int64_t z_begin,
                              int64_t z_end, int want_norm, void* stream);

@@ -1,6 +1,7 @@
 // The handle types behind include/poms_hip.h and the few internals that cross the
-// files of the extern "C" boundary (abi_op.hip, abi_vec.hip, abi_transfer.hip,
-// abi_ksolve.hip, pcg_native.hip; comm.hip and spline_field.hip take declarations only).
+// files of the extern "C" boundary (abi_op.hip, which launches operators, abi_op_setup.hip,
+// which makes and destroys them, abi_vec.hip, abi_transfer.hip, abi_ksolve.hip,
+// pcg_native.hip; comm.hip and spline_field.hip take declarations only).
 // A source that includes this header also names the three headers below itself:
 // build.py's dependency scan reads a source's own quoted includes only.
 #pragma once
@@ -22,12 +23,30 @@ struct poms_ctx {
 struct SpecPart { int64_t off; int n; int kind; int vi; };
 
 // Where one operator launch may write its per-block partials instead of the scratch
-// (op_run_epi's in/out argument): `dst` when all its sums fit in `cap` doubles, norms
+// (OpLaunch::route, in and out): `dst` when all its sums fit in `cap` doubles, norms
 // first, dots behind them; on return `used` says whether they went there.
 struct PartRoute {
     double* dst = nullptr;
     int64_t cap = 0;
     bool used = false;
+};
+
+// One operator launch (op_run_epi and everything behind it): what every launch names, in
+// the order a brace initialiser gives it, then what most leave at its default -- the sums
+// wanted and where their partials may go, a second plane range [zb2, ze2) of axis 0 (the
+// slab's other boundary) and EPI_CHEBY's beta.
+struct OpLaunch {
+    int epi;
+    const double* x;
+    double* y;
+    const double* b;
+    int64_t zb, ze;   // planes of axis 0
+    void* stream;
+    double omega = 0.0;
+    bool want_norm = false, want_dot = false;
+    PartRoute* route = nullptr;
+    int64_t zb2 = 0, ze2 = 0;
+    double beta = 0.0;
 };
 
 // poms_pcg_jacobi's host-sum slots: defined in pcg_native.hip and incomplete everywhere
@@ -37,9 +56,9 @@ struct PcgSlots;
 void pcg_slots_free(PcgSlots* s);
 }  // namespace poms
 
-// Created, configured and destroyed by abi_op.hip.
+// Created and destroyed by abi_op_setup.hip, configured and launched by abi_op.hip.
 struct poms_op {
-    // ---- operator launch state (abi_op.hip; set at creation or by its setters) ----
+    // ---- operator launch state (set at creation or by abi_op.hip's setters) ----
     poms_ctx* ctx = nullptr;
     int ndim = 3, form = poms::FORM_SUM, pmax = 1, chunk = 0, tout = 0;
     poms_layout L{};
@@ -177,6 +196,11 @@ struct poms_ksolve {
 // two-sweeps-from-zero, a stored diagonal): the stored stencil and the matrix-free form
 inline bool general_form(const poms_op* o) { return o->form == poms::FORM_STENCIL || o->form == poms::FORM_MATFREE; }
 
+// a slab of axis 0 or a Cart block: some neighbour's rows act through exchanged ghosts
+inline bool distributed(const poms_op* o) {
+    return o->g0 != 0 || (o->ndim == 3 && o->L.n[0] != o->n0g) || (o->L.flags & POMS_LAYOUT_GHOST_DATA);
+}
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline bool layout_ok(const poms_layout* L) {
@@ -201,6 +225,14 @@ inline poms::RowGeom row_geom(const poms_layout* L) {
     return g;
 }
 
+// the general-stencil kernels' geometry: half-widths sp[3], planes [zb, ze) + [zb2, ze2)
+inline poms::StencilGeom stencil_geom(const poms::RowGeom& r, const int* sp, int64_t zb, int64_t ze, int64_t zb2,
+                                      int64_t ze2, int dmask) {
+    return {r.s0, r.s1, r.n0, r.n1, r.n2, r.pd0, r.pd1, r.pd2, sp[0], sp[1], sp[2],
+            2 * sp[0] + 1, 2 * sp[1] + 1, 2 * sp[2] + 1, (int64_t)r.n0 * r.n1 * r.n2,
+            (int)zb, (int)ze, (int)zb2, (int)ze2, dmask};
+}
+
 // doubles of one of the operator's vectors, ghost planes included
 inline int64_t padded_len(const poms_op* o) { return (int64_t)(o->L.n[0] + 2 * o->L.pads[0]) * row_geom(&o->L).s0; }
 
@@ -216,12 +248,9 @@ namespace poms {
 bool error_is_set();                         // a message is waiting in poms_last_error
 int ctx_device(const poms_ctx* ctx);         // for the sources that see poms_ctx opaque
 bool sweep2_ok(const poms_op* o);
-int op_run_epi(poms_op* op, int epilogue, double omega, const double* x, double* y, const double* b,
-               int64_t zb, int64_t ze, int64_t zb2, int64_t ze2, bool wn, bool wd, void* stream,
-               PartRoute* route = nullptr);
-int op_run_split(poms_op* op, int epilogue, double omega, const double* x, double* y, const double* b,
-                 int64_t ib, int64_t ie, int64_t b1s, int64_t b1e, int64_t b2s, int64_t b2e, double* norm_out,
-                 double* dot_out, const SplitHooks& h, void* stream);
+int op_run_epi(poms_op* op, const OpLaunch& q);
+int op_run_split(poms_op* op, const OpLaunch& interior, int64_t b1s, int64_t b1e, int64_t b2s, int64_t b2e,
+                 double* norm_out, double* dot_out, const SplitHooks& h);
 
 // abi_vec.hip
 int vec_copy_dot(poms_ctx* ctx, const poms_layout* L, const double* x, double* z, double* out_dev,

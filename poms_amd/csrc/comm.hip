@@ -901,9 +901,8 @@ int poms_op_run_dist(poms_op* op, poms_comm* c, int epilogue, double omega, cons
         };
         static const bool on_cs = !getenv_off("POMS_BOUNDARY_ON_CS");
         const SplitHooks h{on_cs ? static_cast<void*>(c->cs) : nullptr, &Hooks::ghosts_on, &Hooks::join, c};
-        if (op_run_split(op, epilogue, omega, x, y, b, pmax, n_local - pmax, 0, pmax, n_local - pmax, n_local, nout,
-                         dout, h, stream))
-            return 1;
+        const OpLaunch interior{epilogue, x, y, b, pmax, n_local - pmax, stream, omega};
+        if (op_run_split(op, interior, 0, pmax, n_local - pmax, n_local, nout, dout, h)) return 1;
     } else {
         if (exchange) {
             if (poms_halo_start(c, xplanes, plane_elems, n_local, pad, pmax, prev, next, stream)) return 1;

@@ -277,6 +277,10 @@ struct PcgRun {
                                 h < 0 ? 0 : (wn ? 1 : 0) + (wd ? 1 : 0), h < 0 ? nullptr : sv.host + h,
                                 h < 0 ? &tk0 : &tk[h], stv);
     }
+    // one rank's launch over the whole axis 0, its partials left for the caller to reduce
+    int launch(int epi, const double* x, double* y, const double* b, bool wn, bool wd, PartRoute* route = nullptr) {
+        return op_run_epi(op, OpLaunch{epi, x, y, b, 0, n0, stv, o->omega, wn, wd, route});
+    }
     int run(int epi, const double* x, double* y, const double* b, double* nrm, double* dot) {
         if (comm) return run_dist(epi, x, y, b, nrm, dot, nrm, dot, -1);
         return poms_op_run_reduce2(op, epi, o->omega, x, y, b, 0, n0, 0, 0, nrm, dot, 0, stv);
@@ -301,7 +305,7 @@ struct PcgRun {
             POMS_HIP_CHECK(hipGetLastError());
             return 0;
         }
-        if (op_run_epi(op, EPI_APPLYDOT, o->omega, p, q, p, 0, n0, 0, 0, false, true, stv)) return 1;
+        if (launch(EPI_APPLYDOT, p, q, p, false, true)) return 1;
         const int64_t n = op->last_partials;   // (the dot's partials at scratch + n, as poms_op_run_reduce2 reads them)
         // alpha is formed by the r update that follows (rupd: AlphaFold), or by
         // pcg_alpha_kernel when that cannot take it (flush_alpha)
@@ -470,13 +474,13 @@ struct PcgRun {
         // host_partials_max() blocks).  A/B on one box (profiles/r03/host_partials/):
         // 2D 1027^2 cycle 4.5-5.2 -> 3.6-3.7 ms, 3D 515^3 195.0-195.5 -> 194.9-195.3 ms
         PartRoute rt{sv.region(h), ((wn ? 1 : 0) + (wd ? 1 : 0)) * PcgSlots::host_partials_max()};
-        if (op_run_epi(op, epi, o->omega, x, y, b, 0, n0, 0, 0, wn, wd, stv, &rt)) return 1;
+        if (launch(epi, x, y, b, wn, wd, &rt)) return 1;
         return sums_tail(op->last_partials, (wn ? 1 : 0) | (wd ? 2 : 0), rt.used, h, -1, sv.host + h);
     }
     // sweeps 1-3 from x = 0 (one rank): [||x1||^2, ||dr_2||^2, ||dr_3||^2] into slots h .. h+2
     int jrun3(const double* rhs, double* y, int h) {
         PartRoute rt{sv.region(h), 3 * PcgSlots::host_partials_max()};
-        if (op_run_epi(op, EPI_JACOBI3Z, o->omega, rhs, y, rhs, 0, n0, 0, 0, true, true, stv, &rt)) return 1;
+        if (launch(EPI_JACOBI3Z, rhs, y, rhs, true, true, &rt)) return 1;
         return sums_tail(op->last_partials, 4, rt.used, h, -1, sv.host + h);
     }
     // `cnt` host slots for the next launch: from the ring, or with a communicator the fixed ones
@@ -609,7 +613,7 @@ struct PcgRun {
         double* dd = wd ? op->spec_dev + vi : nullptr;
         if (!direct()) return run(epi, x, y, b, dn, dd);
         PartRoute rt{op->spec_part + scur, poms_op::kSpecPart - scur};
-        if (op_run_epi(op, epi, o->omega, x, y, b, 0, n0, 0, 0, wn, wd, stv, &rt)) return 1;
+        if (launch(epi, x, y, b, wn, wd, &rt)) return 1;
         return sums_tail(op->last_partials, (wn ? 1 : 0) | (wd ? 2 : 0), rt.used, -1, vi, op->spec_dev + vi);
     }
     // damped_jacobi with every sweep queued (no stop test read); as damped_jacobi below
@@ -709,12 +713,12 @@ struct PcgRun {
                 // stops after sweep 1.  P_PAIR: x_k, one sweep from the launch's input
                 // (intact: only one launch was queued after it)
                 if (f.kind == P_PAIR
-                        ? op_run_epi(op, EPI_JACOBI, o->omega, bufs[f.in], xr, rhs, 0, n0, 0, 0, false, false, stv)
+                        ? launch(EPI_JACOBI, bufs[f.in], xr, rhs, false, false)
                         : poms_op_diag_scale(op, o->omega, rhs, xr, 0, stv))
                     return S_ERR;
                 res = xr;
             } else if (f.kind == P_ZERO3 && get(f.h, 1) < tol2) {   // after sweep 2 of the three: x2
-                if (op_run_epi(op, EPI_JACOBI0, o->omega, rhs, xr, rhs, 0, n0, 0, 0, false, false, stv)) return S_ERR;
+                if (launch(EPI_JACOBI0, rhs, xr, rhs, false, false)) return S_ERR;
                 res = xr;
             } else if (get(f.h, f.kind == P_ZERO3 ? 2 : 1) < tol2) {   // after its last sweep: the launch's output
                 res = bufs[f.buf];
@@ -743,8 +747,7 @@ struct PcgRun {
             if (last) {   // the last sweep's norm cannot change the result: x . rhs instead
                 dot_part_n = -1;
                 if (direct() && dot_idx == SC_SRN && !general_form(op)) {   // its partials wait for pcg_beta_kernel
-                    if (op_run_epi(op, EPI_JACOBI, o->omega, bufs[cur], bufs[nxt], rhs, 0, n0, 0, 0, false, true, stv))
-                        return 1;
+                    if (launch(EPI_JACOBI, bufs[cur], bufs[nxt], rhs, false, true)) return 1;
                     dot_part_n = op->last_partials;
                     dot_part = op->ctx->scratch + dot_part_n;   // (where poms_op_run_reduce2 reads a dot's partials)
                 } else if (run(EPI_JACOBI, bufs[cur], bufs[nxt], rhs, nullptr, sc + dot_idx) || allsum(sc + dot_idx, 1)) {

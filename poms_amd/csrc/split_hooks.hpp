@@ -1,5 +1,5 @@
-// Shared by abi_op.hip (op_run_split, declared in abi_internal.hpp) and comm.hip
-// (poms_op_run_dist).
+// Shared by abi_op.hip (op_run_split, declared in abi_internal.hpp beside its OpLaunch
+// argument) and comm.hip (poms_op_run_dist).
 #pragma once
 
 namespace poms {

@@ -15,7 +15,7 @@
 // runs last, on the array the other two already reduced.  The weights come from a
 // host-built table wt[I][ii][k][kc] = P[lo[I] + ii, I] * P[lo[I] + ii + k - p, I + kc - p]
 // (0 where the column or the row is outside the grid), which is what lets the
-// kernel index unguarded: abi_op.hip validates the factors before any launch.  In the
+// kernel index unguarded: abi_op_setup.hip validates the factors before any launch.  In the
 // axis-0 and axis-1 passes nearly every lane of a wave has the same I and reads the same
 // weight; in the axis-2 pass the lanes differ in I, and its table is stored with the
 // columns contiguous (wt[e][I], GalerkinPass::ws_col = 1) so that consecutive lanes read

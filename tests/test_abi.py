@@ -47,6 +47,13 @@ def test_abi_version_and_error_protocol():
         _lib.call("poms_op_apply", None, None, None, 0, 0, None)
 
 
+def test_variant_built_is_the_variant_table():
+    """poms_variant_built: 1 exactly for 0, 4, 7-10 and the diagnostic builds 90-114."""
+    known = {0, 4, 7, 8, 9, 10} | set(range(90, 115))
+    for v in range(-1, 130):
+        assert _lib.lib.poms_variant_built(v) == (1 if v in known else 0), v
+
+
 def test_gpu_required_calls_fail_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():
