@@ -33,10 +33,11 @@
 extern "C" {
 #endif
 
-#define POMS_ABI_VERSION 9 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
-                            * 7: poms_pcg_opts.n_pbuf, .pbuf;
-                            * 8: poms_op_set_dirichlet, poms_op_get_dirichlet;
-                            * 9: poms_op_cheby_step, poms_op_cheby_supported */
+#define POMS_ABI_VERSION 10 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
+                             * 7: poms_pcg_opts.n_pbuf, .pbuf;
+                             * 8: poms_op_set_dirichlet, poms_op_get_dirichlet;
+                             * 9: poms_op_cheby_step, poms_op_cheby_supported;
+                             * 10: poms_op_papply_dot (+ _supported, _count), poms_pcg_p_update_dev */
 
 /* operator forms (see poms_op_create) */
 #define POMS_FORM_SINGLE 0 /* y = F0 (x) F1 (x) F2 x                                  */
@@ -291,6 +292,20 @@ int poms_op_apply(poms_op* op, const double* x, double* y, int64_t z_begin,
 int poms_op_apply_dot(poms_op* op, const double* x, double* y, int64_t z_begin,
                       int64_t z_end, void* stream);
 int poms_op_apply_dot_supported(poms_op* op, int* yes);
+/* pcg's p update formed inside the apply + dot that follows it, over every plane:
+ * p_next = s + beta_dev[0] p (the fma of poms_pcg_p_update_dev), q = A p_next, and
+ * dot_out[0] (device) = p_next . q, with the bits of poms_pcg_p_update_dev followed by
+ * poms_op_apply_dot on p_next; p_next is never read back.  Only p_next's interior points
+ * are stored: its ghost cells must be zero already.  The four vectors must be distinct.
+ * Where it runs (poms_op_papply_dot_supported): one rank, 3D Kronecker-sum operators at
+ * p <= 3 on kernel variant 8 or 10, p and p_next on the same side of the line alignment
+ * (poms_layout.pitch).  poms_op_papply_dot_count: such launches so far, the native pcg
+ * loop's included (POMS_PCG_PFOLD=0 keeps that loop on the two launches).              */
+int poms_op_papply_dot_supported(poms_op* op, const double* s, const double* p, const double* p_next,
+                                 const double* q, int* yes);
+int poms_op_papply_dot(poms_op* op, const double* beta_dev, const double* s, const double* p,
+                       double* p_next, double* q, double* dot_out, void* stream);
+int poms_op_papply_dot_count(poms_op* op, int64_t* count);
 /* r = b - A x (fused).  Replaces: `r = b - A.dot(x)` at `sources/solvers.py:85`,
  * `sources/solvers.py:209`, `sources/mg_jac.py:93`.                           */
 int poms_op_residual(poms_op* op, const double* b, const double* x, double* r,
@@ -411,6 +426,11 @@ int poms_pcg_r_update_dev(poms_ctx* ctx, const poms_layout* L, const double* alp
                           const double* q, double* out_dev, void* stream);
 int poms_pcg_xp_update_dev(poms_ctx* ctx, const poms_layout* L, const double* ab_dev, double* x, double* p,
                            const double* s, void* stream);
+/* The p half of poms_pcg_xp_update_dev into another vector, as the native loop's deferred
+ * x updates run it: p_next = s + ab_dev[1] p over whole interior planes (the flat kernel;
+ * an error where the layout has ghost data or the vectors differ in their 16-B phase).  */
+int poms_pcg_p_update_dev(poms_ctx* ctx, const poms_layout* L, const double* ab_dev, const double* s,
+                          const double* p, double* p_next, void* stream);
 /* pcg's last iteration when the rest of it is discarded (poms_pcg_opts.skip_tail):
  * x += alpha p (the x half of poms_pcg_xp_update_dev, bitwise) and
  * out_dev[0] = (r - alpha q).(r - alpha q) (poms_pcg_r_update_dev's sum, bitwise).

@@ -34,7 +34,8 @@ struct PartRoute {
 // One operator launch (op_run_epi and everything behind it): what every launch names, in
 // the order a brace initialiser gives it, then what most leave at its default -- the sums
 // wanted and where their partials may go, a second plane range [zb2, ze2) of axis 0 (the
-// slab's other boundary) and EPI_CHEBY's beta.
+// slab's other boundary), EPI_CHEBY's beta, and EPI_PAPPLYDOT's second output y2 = b + beta x
+// with its beta on the device.
 struct OpLaunch {
     int epi;
     const double* x;
@@ -47,6 +48,8 @@ struct OpLaunch {
     PartRoute* route = nullptr;
     int64_t zb2 = 0, ze2 = 0;
     double beta = 0.0;
+    double* y2 = nullptr;
+    const double* beta_dev = nullptr;
 };
 
 // poms_pcg_jacobi's host-sum slots: defined in pcg_native.hip and incomplete everywhere
@@ -98,6 +101,7 @@ struct poms_op {
     // blocks of the last launch's partials (op_run, stencil_run, poms_op_diag_scale;
     // pcg_native.hip's diag_scale_norm writes it too)
     int64_t last_partials = 0;
+    int64_t papply_launches = 0;   // EPI_PAPPLYDOT launches so far (poms_op_papply_dot_count)
 
     // ---- native pcg loop (pcg_native.hip only; freed by poms_op_destroy) ----
     double* sv_dev = nullptr;        // device scalars, then the deferred x pass's alphas
@@ -248,6 +252,9 @@ namespace poms {
 bool error_is_set();                         // a message is waiting in poms_last_error
 int ctx_device(const poms_ctx* ctx);         // for the sources that see poms_ctx opaque
 bool sweep2_ok(const poms_op* o);
+// EPI_PAPPLYDOT can run y2 = b + beta x, y = A y2 on these vectors with the bits of the flat
+// p update followed by EPI_APPLYDOT on y2 (papply_ok's comment in abi_op.hip)
+bool papply_ok(const poms_op* o, const double* x, const double* b, const double* y2, const double* y);
 int op_run_epi(poms_op* op, const OpLaunch& q);
 int op_run_split(poms_op* op, const OpLaunch& interior, int64_t b1s, int64_t b1e, int64_t b2s, int64_t b2e,
                  double* norm_out, double* dot_out, const SplitHooks& h);

@@ -294,6 +294,19 @@ static int resolve_variant(const poms_op* o, int epi) {
     return v;
 }
 
+// EPI_PAPPLYDOT (kron_v5.hip): y2 = b + beta x formed inside the apply + dot of y2.  It runs
+// where v5 runs its 16-wave tiles (3D FORM_SUM, p <= 3; not the diagnostic builds) on one
+// rank without ghost data (the launch stores y2's interior points only: its pads must be
+// zero already, as the flat update would have written them), and where the launch takes the
+// tile geometry of the apply + dot on y2 it replaces, so that q and the p.q partials keep
+// their bits: x and y2 on the same side of v5's line alignment.
+bool poms::papply_ok(const poms_op* o, const double* x, const double* b, const double* y2, const double* y) {
+    if (!o || !x || !b || !y2 || !y || x == b || x == y2 || x == y || b == y2 || b == y || y2 == y) return false;
+    if (general_form(o) || distributed(o) || o->pmax > 3 || o->variant > 10) return false;
+    if (resolve_variant(o, EPI_PAPPLYDOT) != 10) return false;
+    return v5_aligned(o, x) == v5_aligned(o, y2);
+}
+
 // Two Jacobi sweeps per launch (EPI_JACOBI2, kron_2d.hip): one-rank 2D p = 3
 // Kronecker operators whose single sweep runs the v3 whole-array kernel (variant 9),
 // whose bits the two-sweep kernel reproduces
@@ -407,6 +420,10 @@ static int op_run(poms_op* o, const OpLaunch& q) {
     const bool want_norm = q.want_norm, want_dot = q.want_dot;
     if (!o || !q.x || !q.y) { set_error("null operator or vector"); return 1; }
     if (epi != EPI_APPLY && !q.b) { set_error("null right-hand side"); return 1; }
+    if (epi == EPI_PAPPLYDOT && (!q.beta_dev || !papply_ok(o, q.x, q.b, q.y2, q.y))) {
+        set_error("p update + apply + x.y: v5's 16-wave tiles on one rank, five distinct arguments (poms_op_papply_dot_supported)");
+        return 1;
+    }
     if (epi == EPI_JACOBI2 || epi == EPI_JACOBI3Z) return op_run_j2(o, q);
     if (o->form == FORM_STENCIL) return stencil_run(o, q);
     if (o->form == FORM_MATFREE) return matfree_run(o, q);
@@ -415,7 +432,8 @@ static int op_run(poms_op* o, const OpLaunch& q) {
         set_error("apply + x.y: kernel variants 4, 8, 9, 10 only");
         return 1;
     }
-    if (want_dot && ((epi != EPI_JACOBI && epi != EPI_JACOBI0 && epi != EPI_APPLYDOT) || !fused_dot_ok(o))) {
+    if (want_dot && ((epi != EPI_JACOBI && epi != EPI_JACOBI0 && epi != EPI_APPLYDOT && epi != EPI_PAPPLYDOT) ||
+                     !fused_dot_ok(o))) {
         set_error("fused x_out.b needs a Jacobi sweep on kernel variants 4-10");
         return 1;
     }
@@ -443,7 +461,7 @@ static int op_run(poms_op* o, const OpLaunch& q) {
     double *pn = nullptr, *pd = nullptr;
     if (part_place(o, nblk, want_norm, want_dot, false, q.route, &pn, &pd)) return 1;
     KronPtrs p{q.x, q.y, q.b, o->a0t, o->b0t, o->a1, o->b1, o->a2, o->b2, want_norm ? pn : nullptr,
-               want_dot ? pd : nullptr, o->rdiag0};
+               want_dot ? pd : nullptr, o->rdiag0, q.y2, q.beta_dev};
     poms_op::TimedLaunch* tlh = nullptr;
     bool tl_ext = false;
     if (timing_begin(o, q, v, g, &tlh, &tl_ext)) return 1;
@@ -458,6 +476,7 @@ static int op_run(poms_op* o, const OpLaunch& q) {
     if (timing_end(q, tlh, tl_ext, rc) || rc) return 1;
     POMS_HIP_CHECK(hipGetLastError());
     o->last_partials = (want_norm || want_dot) ? nblk : 0;
+    if (epi == EPI_PAPPLYDOT) ++o->papply_launches;
     return 0;
 }
 
@@ -501,6 +520,11 @@ int poms::op_run_epi(poms_op* op, const OpLaunch& in) {
             if (q.x == q.y) { set_error("apply: y must not alias x"); return 1; }
             if (wn || !wd) { set_error("apply + dot: dot_out only"); return 1; }
             break;
+        case EPI_PAPPLYDOT:   // y2 = b + beta x, y = A y2, dot_out <- y2 . y
+            // (poms_op_run_reduce cannot name y2 and beta: not one of its epilogues)
+            if (!q.y2 || !q.beta_dev) { set_error("poms_op_run_reduce: bad epilogue"); return 1; }
+            if (wn || !wd) { set_error("p update + apply + dot: dot_out only"); return 1; }
+            break;
         default:
             set_error("poms_op_run_reduce: bad epilogue");
             return 1;
@@ -509,7 +533,7 @@ int poms::op_run_epi(poms_op* op, const OpLaunch& in) {
     const int e = q.epi;
     if (e == EPI_APPLY) q.b = nullptr;
     if (e == EPI_APPLYDOT) q.b = q.x;
-    if (e == EPI_APPLY || e == EPI_RESID || e == EPI_APPLYDOT) q.omega = 0.0;
+    if (e == EPI_APPLY || e == EPI_RESID || e == EPI_APPLYDOT || e == EPI_PAPPLYDOT) q.omega = 0.0;
     if (e == EPI_APPLY || e == EPI_RESID) q.route = nullptr;   // (no sums: the route stays as it came)
     if (e == EPI_JACOBI0 || e == EPI_JACOBI3Z) q.x = q.b;
     if (e == EPI_JACOBI2 || e == EPI_JACOBI3Z) q.zb2 = q.ze2 = 0;
@@ -769,6 +793,35 @@ int poms_op_cheby_supported(poms_op* op, int* yes) {
 int poms_op_apply_dot_supported(poms_op* op, int* yes) {
     if (!op || !yes) { set_error("poms_op_apply_dot_supported: null argument"); return 1; }
     *yes = (general_form(op) || variant_can(op, CAP_APPLY_DOT)) ? 1 : 0;
+    return 0;
+}
+
+int poms_op_papply_dot_supported(poms_op* op, const double* s, const double* p, const double* p_next, const double* q,
+                                 int* yes) {
+    if (!op || !yes) { set_error("poms_op_papply_dot_supported: null argument"); return 1; }
+    *yes = papply_ok(op, p, s, p_next, q) ? 1 : 0;
+    return 0;
+}
+
+int poms_op_papply_dot(poms_op* op, const double* beta_dev, const double* s, const double* p, double* p_next,
+                       double* q, double* dot_out, void* stream) {
+    if (!op || !beta_dev || !s || !p || !p_next || !q || !dot_out) { set_error("poms_op_papply_dot: null argument"); return 1; }
+    OpLaunch l{EPI_PAPPLYDOT, p, q, s, 0, op->L.n[0], stream, 0.0, false, true};
+    l.y2 = p_next;
+    l.beta_dev = beta_dev;
+    if (op_run_epi(op, l)) return 1;
+    const int64_t n = op->last_partials;
+    if (reduce_launch(op->ctx->scratch + n, (int)n, dot_out, as_stream(stream))) {
+        set_error("poms_op_papply_dot: reduction launch failed");
+        return 1;
+    }
+    POMS_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int poms_op_papply_dot_count(poms_op* op, int64_t* count) {
+    if (!op || !count) { set_error("poms_op_papply_dot_count: null argument"); return 1; }
+    *count = op->papply_launches;
     return 0;
 }
 

@@ -129,6 +129,21 @@ int poms_pcg_xp_update_dev(poms_ctx* ctx, const poms_layout* L, const double* ab
     return vec_common(ctx, L, V_XPUPD, 0.0, 0.0, s, nullptr, x, p, nullptr, nullptr, stream, ab_dev);
 }
 
+int poms_pcg_p_update_dev(poms_ctx* ctx, const poms_layout* L, const double* ab_dev, const double* s,
+                          const double* p, double* p_next, void* stream) {
+    if (!ctx || !layout_ok(L) || !s || !p || !p_next || !ab_dev) { set_error("pcg_p_update_dev: bad argument"); return 1; }
+    const FlatRange fr = flat_range(row_geom(L));
+    int nb = 0;
+    if ((L->flags & POMS_LAYOUT_GHOST_DATA) ||
+        vec_flat_launch(V_PUPD, fr.count, 0.0, 0.0, s + fr.off, p + fr.off, p_next + fr.off, nullptr, nullptr, nullptr,
+                        as_stream(stream), &nb, ab_dev)) {
+        set_error("pcg_p_update_dev: needs whole interior planes and one 16-B phase");
+        return 1;
+    }
+    POMS_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // pcg's last iteration when what follows it is discarded (poms_pcg_opts.skip_tail):
 // x += alpha p with V_XPUPD's statement, (r - alpha q).(r - alpha q) with V_RUPD's.
 // r - alpha q is not kept: r's buffer takes x as the early-stop update would have

@@ -151,7 +151,7 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
                const double* __restrict__ a2, const double* __restrict__ b2,
                double* __restrict__ partial, double* __restrict__ partial2,
                const double* __restrict__ rdiag0, const KronGeom g, const ToepConst tc,
-               const int H, const double omega) {
+               const int H, const double omega, double* __restrict__ y2, const double* __restrict__ betap) {
     constexpr int W = 2 * P + 1;
     constexpr int NW = v5_waves(P, EPI, SAME12);
     constexpr int T1 = NW;              // output rows per tile: one per wave
@@ -161,7 +161,9 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     constexpr int PFX = D - 1;          // x prefetch distance (planes)
     constexpr bool HASB = (EPI == EPI_RESID) || (EPI == EPI_JACOBI);
     constexpr bool JAC = (EPI == EPI_JACOBI);
-    constexpr bool APD = (EPI == EPI_APPLYDOT);
+    // PAPD: apply + dot of y2 = b + beta x, formed in the x ring (see papd_combine below)
+    constexpr bool PAPD = (EPI == EPI_PAPPLYDOT);
+    constexpr bool APD = (EPI == EPI_APPLYDOT) || PAPD;
     // two sweeps from x = 0: the x ring holds b, scaled on the fly to x1 = omega b / diag
     constexpr bool J0 = (EPI == EPI_JACOBI0);
     constexpr bool HIST = APD || (JAC && XH) || J0;   // x (J0: x1) at the output point from a register history
@@ -180,6 +182,8 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     constexpr int NXM = (XR + NW - 1) / NW;   // most x-row DMAs one wave issues per plane
     static_assert(NXM >= 2 && (NXM - 1) * NW < XR, "x tile rows vs waves");
     static_assert(D >= 3 || !HASB, "the b ring's wait count assumes x(t) was issued before b(t)");
+    static_assert(!PAPD || (NW == 16 && NXM == 2 && D == 4 && MODE == 0),
+                  "PAPD: 16-wave tiles (every wave owns one output row of the x tile), x three planes ahead");
     typedef double d2 __attribute__((ext_vector_type(2)));
 
     constexpr int XS_OFF = 0;
@@ -187,7 +191,10 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     // issuing x before b (so that b(t) landing still implies x(t), PFX = 2)
     constexpr bool B3 = HASB && (CP & 64) && !XIN && D == 3;   // (x_in DMA builds and deeper x rings keep the 2-deep b ring)
     constexpr int NB = B3 ? 3 : 2;      // b ring depth
-    constexpr int BS_OFF = XS_OFF + D * XR * TC;
+    // PAPD: the b rows (pcg's s) of the two planes DMA'd but not yet combined; every wave
+    // reads back only the rows it DMA'd itself
+    constexpr int SS_OFF = XS_OFF + D * XR * TC;
+    constexpr int BS_OFF = SS_OFF + (PAPD ? 2 * XR * TC : 0);
     constexpr int XI_OFF = BS_OFF + (HASB ? NB * T1 * TC : 0);
     constexpr int C2_OFF = XI_OFF + (XIN ? 2 * T1 * TC : 0);
     constexpr int RED_OFF = C2_OFF + 2 * W * TC;
@@ -333,8 +340,9 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     const uint32_t arr_bytes = (uint32_t)((int64_t)nsp * g.s0 * 8);
     const uint32_t plane8 = (uint32_t)(g.s0 * 8);
     const __amdgpu_buffer_rsrc_t rx = make_rsrc(x, arr_bytes);
-    const __amdgpu_buffer_rsrc_t rbv = make_rsrc(bvec, HASB ? arr_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t rbv = make_rsrc(bvec, (HASB || PAPD) ? arr_bytes : 0u);
     const __amdgpu_buffer_rsrc_t ry = make_rsrc(y, arr_bytes);
+    const __amdgpu_buffer_rsrc_t ry2 = make_rsrc(y2, PAPD ? arr_bytes : 0u);
     auto zo_of = [&](int t) { return max(z0 - 2 * P + t, z0); };
     // storage column of lane-column 0 (pads == P): c0 - H + P
     const int colb = (c0 - H + P) * 8 + 16 * lane;
@@ -356,8 +364,8 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     // last tile row at 515^3: 9 of its 22 rows) are not fetched either
     const int xrows_ok = g.n1 + 2 * P - r0;
 
-    // ---- LDS-DMA issue (per wave per plane: x NXM - 1 or NXM rows, b 1 row) ----
-    auto dma_x = [&](int m, int slot) {
+    // ---- LDS-DMA issue (per wave per plane: x NXM - 1 or NXM rows, b 1 row; PAPD: its b rows as x's) ----
+    auto dma_rows = [&](const __amdgpu_buffer_rsrc_t rsrc, const int ring, int m, int slot) {
         if constexpr (MODE == 2) return;
         const int sp = m + g.pd0;
         // planes outside the array (the dummies past the march) are out of range by
@@ -367,16 +375,17 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
         // x-tile row q = storage row r0 + q (rows q >= xrows_ok: out of range by voffset)
         const bool ok0 = ok && wv < xrows_ok;
         if ((CP & 8) && wv >= 2 * P)   // a row only this tile reads: stream it
-            dma16s<2>(rx, lds + XS_OFF + (slot * XR + wv) * TC, ok0 ? (int)((uint32_t)((r0 + wv) * s1 * 8) + colbx) : 0x7ffffff0, so);
+            dma16s<2>(rsrc, lds + ring + (slot * XR + wv) * TC, ok0 ? (int)((uint32_t)((r0 + wv) * s1 * 8) + colbx) : 0x7ffffff0, so);
         else
-            dma16s<XAUX>(rx, lds + XS_OFF + (slot * XR + wv) * TC, ok0 ? (int)((uint32_t)((r0 + wv) * s1 * 8) + colbx) : 0x7ffffff0, so);
+            dma16s<XAUX>(rsrc, lds + ring + (slot * XR + wv) * TC, ok0 ? (int)((uint32_t)((r0 + wv) * s1 * 8) + colbx) : 0x7ffffff0, so);
 #pragma unroll
         for (int i = 1; i < NXM; ++i)   // rows wv + i NW: every wave but the last on the tile's x rows
             if (i < NXM - 1 || wv < XR - (NXM - 1) * NW)
-                dma16s<XAUX>(rx, lds + XS_OFF + (slot * XR + i * NW + wv) * TC,
+                dma16s<XAUX>(rsrc, lds + ring + (slot * XR + i * NW + wv) * TC,
                              (ok && i * NW + wv < xrows_ok) ? (int)((uint32_t)((r0 + i * NW + wv) * s1 * 8) + colbx)
                                                             : 0x7ffffff0, so);
     };
+    auto dma_x = [&](int m, int slot) { dma_rows(rx, XS_OFF, m, slot); };
     auto dma_b = [&](int zo, int slot) {
         const uint32_t so = (uint32_t)(zo + g.pd0) * plane8;
         const int vob = row_ok ? (int)((uint32_t)((orow + P) * s1 * 8) + colbb) : 0x7ffffff0;   // (no output row: no b)
@@ -407,7 +416,7 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     // in the driver's bench line (round-4 verdict).
     if constexpr (ZR && (MODE == 0 || MODE == 6)) {
         // (x ring, then b and x_in rings: contiguous from XS_OFF)
-        static_assert(BS_OFF == XS_OFF + D * XR * TC && XI_OFF == BS_OFF + (HASB ? NB * T1 * TC : 0), "ring layout");
+        static_assert(BS_OFF == SS_OFF && XI_OFF == BS_OFF + (HASB ? NB * T1 * TC : 0), "ring layout");
         constexpr int NZ = (XI_OFF + (XIN ? 2 * T1 * TC : 0) - XS_OFF) / 2;
 #pragma unroll 1
         for (int e = tid; e < NZ; e += NW * 64) *(d2*)(lds + XS_OFF + 2 * e) = d2{0.0, 0.0};
@@ -446,6 +455,65 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     if constexpr (B3) dma_b(zo_of(1), 1);
 
     const bool xtra = wv < XR - (NXM - 1) * NW;   // this wave issues NXM x DMAs per plane (else NXM - 1)
+
+    // ---- PAPD: the ring holds y2 = fma(beta, x, b) (pcg: p_next = s + beta p, V_PUPD's fma).
+    // A wave combines the x-tile rows it DMA'd itself -- x into the ring slot, b beside it
+    // into the staging slot -- after its own vmcnt wait, one plane ahead of the plane being
+    // computed, and writes the result over x in the ring: nothing another wave touches until
+    // the next plane's barrier, which waits for this wave's LDS writes (v5_lds_barrier).
+    // The b rows of plane t+3 go into the staging slot the combine of plane t+1 has just
+    // read (wave-private: the reads have returned, their values are in the ring).  Every
+    // wave has exactly one of the tile's T1 output rows among its rows (x-tile row wv at
+    // wv >= P, else wv + NW) and stores it to y2 on the planes the chunk owns, the tile's
+    // output columns only: every interior point once; the halo points are recomputed by the
+    // neighbouring tiles with the same fma.
+    // Loads per wave, in issue order (X, B: the n = 1 or 2 row DMAs of a plane's x, b):
+    //   X0 X1 X2 B0 B1 [combine 0] B2 | t = 0: X3 [combine 1] B3 | t = 1: X4 [combine 2] B4 | ...
+    // The combine of plane t+1 waits for B(t+1) (X(t+1) is older): at t = 0 B2, X3 follow
+    // it, vmcnt(2n); later X(t+2), B(t+2), X(t+3), vmcnt(3n); combine 0: B1, vmcnt(n).
+    double pbeta = 0.0;
+    if constexpr (PAPD) pbeta = betap[0];
+    auto dma_s = [&](int pl) { dma_rows(rbv, SS_OFF, pl < nplanes ? z0 - P + pl : -(1 << 20), pl & 1); };
+    auto papd_combine = [&](int pl) {   // march plane pl (local plane z0 - P + pl)
+        if (pl >= nplanes) return;      // (a dummy past the march)
+        __asm__ volatile("" ::: "memory");   // (no LDS read moves above the caller's vmcnt wait)
+        const int m = z0 - P + pl;
+        const bool own = m >= z0 && m < z1;
+        double* xr = lds + XS_OFF + (pl % D) * XR * TC + 2 * lane;
+        const double* sr = lds + SS_OFF + (pl & 1) * XR * TC + 2 * lane;
+#pragma unroll
+        for (int i = 0; i < NXM; ++i) {
+            if (i == 0 || xtra) {
+                const int row = i * NW + wv;
+                d2 a = *(const d2*)(xr + row * TC);
+                const d2 s = *(const d2*)(sr + row * TC);
+                a[0] = __builtin_fma(pbeta, a[0], s[0]);
+                a[1] = __builtin_fma(pbeta, a[1], s[1]);
+                *(d2*)(xr + row * TC) = a;
+                if (own && i == (wv >= P ? 0 : 1) && r0 + row - P < g.n1) {   // the wave's output row
+                    const int vo = (r0 + row) * s1 * 8 + colb + (m + g.pd0) * (int)plane8;
+                    const int vs = (cok & 1) ? vo : 0x7ffffff0;
+                    const double a1 = (cok & 2) ? a[1] : 0.0;   // (past n2: a ghost or dead pitch column stays 0)
+                    if constexpr (ST16) {
+                        bstore2_sp<YAUX>(ry2, vs, 0u, a[0], a1);
+                    } else {
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, a[0]), ry2, vs, 0, YAUX);
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, a1), ry2,
+                                                              (cok & 1) ? vo + 8 : 0x7ffffff0, 0, YAUX);
+                    }
+                }
+            }
+        }
+        __asm__ volatile("" ::: "memory");   // (the staging slot is re-filled only after these reads)
+    };
+    if constexpr (PAPD) {
+        dma_s(0);
+        dma_s(1);
+        if (xtra) v5_wait_vm<NXM>();
+        else v5_wait_vm<NXM - 1>();
+        papd_combine(0);
+        dma_s(2);
+    }
     for (int tb = 0; tb < nplanes; tb += NS) {
 #pragma unroll
         for (int q = 0; q < NS; ++q) {
@@ -472,6 +540,9 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
                     if (t == 0) v5_wait_vm<0>();
                     else if (xtra) v5_wait_vm<NXM>();
                     else v5_wait_vm<NXM - 1>();
+                } else if constexpr (PAPD) {
+                    // plane t was waited for and combined one plane ago: the barrier below
+                    // waits for this wave's ring writes instead
                 } else {
                     if (t < PFX) v5_wait_vm<0>();
                     else if (xtra) v5_wait_vm<(PFX - 1) * NXM>();
@@ -482,7 +553,8 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
                     st_b = __builtin_amdgcn_s_memtime();
                     st_wait += st_b - st_a;
                 }
-                v5_barrier();
+                if constexpr (PAPD) v5_lds_barrier();
+                else v5_barrier();
                 // Every wave starts the plane at a high issue priority and drops it for
                 // the plane's axis-0 scatter and epilogue.  A SIMD's four waves otherwise
                 // run in age order: the oldest finishes each plane first and then waits
@@ -499,6 +571,17 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
                 } else {
                     if constexpr (HASB) dma_b(zo_of(t + 1), (t + 1) & 1);
                     dma_x(t + PFX < nplanes ? z0 - P + t + PFX : -(1 << 20), (t + PFX) % D);
+                }
+                if constexpr (PAPD) {   // (the counts: see papd_combine)
+                    if (t == 0) {
+                        if (xtra) v5_wait_vm<2 * NXM>();
+                        else v5_wait_vm<2 * (NXM - 1)>();
+                    } else {
+                        if (xtra) v5_wait_vm<3 * NXM>();
+                        else v5_wait_vm<3 * (NXM - 1)>();
+                    }
+                    papd_combine(t + 1);
+                    dma_s(t + PFX);
                 }
 
                 // J0: the ring holds b; x1 = s b with s = omega / diag.  On a row-Toeplitz tile
@@ -906,13 +989,15 @@ static int v5_launch_t2(const KronPtrs& p, const KronGeom& g, const ToepConst& t
     if (t_v5_ev0 != nullptr) {   // a timed launch: the events on the dispatch itself
         hipExtLaunchKernelGGL((kron_v5_kernel<P, EPI, D, MODE, CP, XH, ST16, JDOT, SAME12>), dim3(nblk),
                               dim3(64 * v5_waves(P, EPI, SAME12)), 0, st, t_v5_ev0, t_v5_ev1, 0, p.x, p.y, p.b, p.a0t,
-                              p.b0t, p.a1, p.b1, p.a2, p.b2, p.partial, p.partial2, p.rdiag0, g, tc, H, omega);
+                              p.b0t, p.a1, p.b1, p.a2, p.b2, p.partial, p.partial2, p.rdiag0, g, tc, H, omega,
+                       p.y2, p.beta);
         t_v5_ev0 = t_v5_ev1 = nullptr;
         t_v5_ev_used = true;
         return 0;
     }
     hipLaunchKernelGGL((kron_v5_kernel<P, EPI, D, MODE, CP, XH, ST16, JDOT, SAME12>), dim3(nblk), dim3(64 * v5_waves(P, EPI, SAME12)), 0, st, p.x,
-                       p.y, p.b, p.a0t, p.b0t, p.a1, p.b1, p.a2, p.b2, p.partial, p.partial2, p.rdiag0, g, tc, H, omega);
+                       p.y, p.b, p.a0t, p.b0t, p.a1, p.b1, p.a2, p.b2, p.partial, p.partial2, p.rdiag0, g, tc, H, omega,
+                       p.y2, p.beta);
     return 0;
 }
 
@@ -936,8 +1021,10 @@ static int v5_launch_t(const KronPtrs& p, const KronGeom& g, const ToepConst& tc
                        hipStream_t st) {
     // (the p = 3 two-sweeps-from-zero build with distinct axis-1 / axis-2 Toeplitz
     // rows spills at 16 waves; resolve_variant leaves that case to v3)
+    // (EPI_PAPPLYDOT: its second output as well)
     const bool st16 = ((reinterpret_cast<uintptr_t>(p.y) + 8 * (int64_t)(g.pd2 - H)) & 15) == 0 &&
-                      g.s1 % 2 == 0 && g.s0 % 2 == 0;
+                      g.s1 % 2 == 0 && g.s0 % 2 == 0 &&
+                      (EPI != EPI_PAPPLYDOT || ((reinterpret_cast<uintptr_t>(p.y2) + 8 * (int64_t)(g.pd2 - H)) & 15) == 0);
     // the Jacobi x_in history does not fit the VGPRs beside the split stores: the
     // unaligned build DMAs x_in next to b instead
     constexpr bool XHU = (EPI == EPI_JACOBI) ? false : XH;
@@ -991,6 +1078,11 @@ static int v5_launch_p(int epi, const KronPtrs& p, const KronGeom& g, const Toep
                            // zeroed rings: POMS_V5_STORE applies to the apply only)
             return v5_launch_t<P, EPI_JACOBI, 4, 0, 6 | 64, true>(p, g, tc, H, omega, st);
         case EPI_APPLYDOT: return v5_launch_t<P, EPI_APPLYDOT, 4, 0, 6>(p, g, tc, H, omega, st);
+        // apply + dot of y2 = b + beta x formed in the ring: the apply + dot's policies, y2 stored
+        // as y; the 16-wave builds only (its combine gives every wave one output row of the x tile)
+        case EPI_PAPPLYDOT:
+            if constexpr (P <= 3) return v5_launch_t<P, EPI_PAPPLYDOT, 4, 0, 6>(p, g, tc, H, omega, st);
+            break;
         // x ring = b (read once, apply's policy), scaled to x1 as it is read; y = x2
         // streamed
         case EPI_JACOBI0: return v5_launch_t<P, EPI_JACOBI0, 4, 0, 14>(p, g, tc, H, omega, st);

@@ -297,8 +297,48 @@ struct PcgRun {
         if (from_part) hipLaunchKernelGGL(pcg_beta_kernel, dim3(1), dim3(256), 0, st, dot_part, (int)dot_part_n, sc);
         else hipLaunchKernelGGL(pcg_scalars_kernel, dim3(1), dim3(64), 0, st, sc, 1, (double*)nullptr);
     }
+    // ---- the p update formed inside the next apply + dot (EPI_PAPPLYDOT) ----
+    // Where that launch runs (papply_ok), pupd only forms beta and remembers its operands;
+    // the next iteration's apd_alpha launches p_next = s + beta p, q = A p_next, p_next . q
+    // in one pass -- V_PUPD's fma, the apply + dot's tiles and partial slots: the same bits --
+    // and p_next is never read back for the apply.  Where no apply follows, flush_pupd
+    // runs the remembered update as the plain V_PUPD launch.
+    const double *rem_s = nullptr, *rem_p = nullptr;
+    double* rem_pn = nullptr;   // null: no p update remembered
+    static bool pfold_on() {    // POMS_PCG_PFOLD=0: always the two launches (A-B; read per call: the
+        const char* e = getenv("POMS_PCG_PFOLD");   // tests run both in one process)
+        return !(e && e[0] == '0');
+    }
+    int pupd_plain(const double* s, const double* p, double* pn, const AlphaFold* bf) {
+        int nb = 0;
+        if (vec_flat_launch(V_PUPD, dcount, 0.0, 0.0, s + doff, p + doff, pn + doff, nullptr, nullptr, nullptr, st, &nb,
+                            sc + SC_ALPHA2, bf)) {
+            set_error("pcg: deferred p update not launched");
+            return 1;
+        }
+        POMS_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    int flush_pupd() {
+        if (!rem_pn) return 0;
+        double* pn = rem_pn;
+        rem_pn = nullptr;
+        return pupd_plain(rem_s, rem_p, pn, nullptr);
+    }
     // q = A p, p.q and alpha: one rank folds p.q's reduction into the alpha kernel
     int apd_alpha(const double* p, double* q) {
+        if (rem_pn) {   // p is the remembered p_next, not formed yet: formed by this launch
+            if (p != rem_pn) { set_error("pcg: the remembered p update is not the apply's vector"); return 1; }
+            OpLaunch l{EPI_PAPPLYDOT, rem_p, q, rem_s, 0, n0, stv, 0.0, false, true};
+            l.y2 = rem_pn;
+            l.beta_dev = sc + SC_BETA;
+            if (op_run_epi(op, l)) { (void)flush_pupd(); return 1; }
+            rem_pn = nullptr;
+            const int64_t n = op->last_partials;
+            alpha_part = op->ctx->scratch + n;
+            alpha_n = n;
+            return 0;
+        }
         if (comm || general_form(op)) {
             if (run(EPI_APPLYDOT, p, q, p, nullptr, sc + SC_PQ) || allsum(sc + SC_PQ, 1)) return 1;
             launch_alpha(nullptr, 0);
@@ -400,9 +440,22 @@ struct PcgRun {
     }
     // pn = s + beta p (V_XPUPD's p, x untouched): beta folded where xpupd_beta folds it,
     // else from pcg_beta_kernel / pcg_scalars_kernel as the plain x/p update takes it
-    int pupd(const double* s, const double* p, double* pn, bool part) {
-        const bool fold = part && fold_on() && dot_part_n * vec_flat_blocks(dcount, pn + doff) <= kFoldReadsMax;
+    // q: where the next iteration's apply + dot writes (pupd may leave the update to that launch)
+    int pupd(const double* s, const double* p, double* pn, bool part, const double* q) {
+        // (n_pbuf >= 2, and a psolve buffer is never a p buffer)
+        if (pn == p || pn == s || p == s) { set_error("pcg: the p update's three vectors must be distinct"); return 1; }
         if (fix_sr()) return 1;   // (beta reads s.r_old at sc[SC_SR])
+        if (pfold_on() && papply_ok(op, p, s, pn, q)) {
+            // beta from the one-block kernel (the launch that forms p_next reads it from
+            // sc[SC_BETA]; the folded beta's bits are this kernel's)
+            launch_beta(part);
+            POMS_HIP_CHECK(hipGetLastError());
+            rem_s = s;
+            rem_p = p;
+            rem_pn = pn;
+            return 0;
+        }
+        const bool fold = part && fold_on() && dot_part_n * vec_flat_blocks(dcount, pn + doff) <= kFoldReadsMax;
         AlphaFold bf;
         if (fold) {
             bf.part = dot_part;
@@ -411,13 +464,7 @@ struct PcgRun {
         } else {
             launch_beta(part);
         }
-        int nb = 0;
-        if (vec_flat_launch(V_PUPD, dcount, 0.0, 0.0, s + doff, p + doff, pn + doff, nullptr, nullptr, nullptr, st, &nb,
-                            sc + SC_ALPHA2, fold ? &bf : nullptr)) {
-            set_error("pcg: deferred p update not launched");
-            return 1;
-        }
-        POMS_HIP_CHECK(hipGetLastError());
+        if (pupd_plain(s, p, pn, fold ? &bf : nullptr)) return 1;
         if (fold) sr_stale = true;
         return 0;
     }
@@ -1112,7 +1159,10 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
     int pring = 0;   // deferred: the p buffer p_{k+1} goes to
     double nrmr = nrmr0 * nrmr0;
     for (k = 1; k <= o->maxiter; ++k) {
-        if (R.defer && R.push_term(p)) return 1;   // (before the launch that forms alpha_k)
+        if (R.defer && R.push_term(p)) {   // (before the launch that forms alpha_k)
+            (void)R.flush_pupd();          // (an error path: no apply follows a remembered p update)
+            return 1;
+        }
         if (R.apd_alpha(p, q)) return 1;
         const int hrr = R.arm(H_RR, 1);
         if (R.defer && o->skip_tail && k == o->maxiter) {
@@ -1151,7 +1201,7 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
         if (R.defer) {   // p_{k+1} into the next p buffer; x first where that one still holds a pending term
             double* pn = o->pbuf[pring];
             if (R.is_pending(pn) && R.xflush(false)) return 1;
-            if (R.pupd(sn, p, pn, dd && R.dot_part_n >= 0)) return 1;
+            if (R.pupd(sn, p, pn, dd && R.dot_part_n >= 0, q)) return 1;   // (may leave it to the next apply + dot)
             p = pn;
             pring = (pring + 1) % npb;
             continue;
@@ -1169,6 +1219,9 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
     // psolve writes s.r before anything reads it)
     R.sr_stale = false;
     if (R.flush_alpha()) return 1;
+    // a p update still remembered (the loop ran out right after it): the plain launch, so
+    // that the p buffers hold what they held without the fused launch
+    if (R.flush_pupd()) return 1;
     // deferred: the terms still pending when the loop ran out (maxiter >= 1: from x0 = None
     // at least one x pass has run by now, x is written)
     if (R.defer && R.xflush(false)) return 1;

@@ -883,6 +883,36 @@ class KronOperator:
             return V.device_sum(nb[4:5])
         return V.global_dot(float(nb[4].item()))
 
+    def papply_dot_supported(self, s: StencilVector, p: StencilVector, p_next: StencilVector,
+                             q: StencilVector) -> bool:
+        """Whether :meth:`papply_dot` runs on these vectors (``poms_op_papply_dot_supported``)."""
+        self._check(s, p, p_next, q)
+        v = C.c_int()
+        _lib.call("poms_op_papply_dot_supported", self._h, rt.ptr(s._data), rt.ptr(p._data), rt.ptr(p_next._data),
+                  rt.ptr(q._data), C.byref(v))
+        return bool(v.value)
+
+    def papply_dot(self, beta: torch.Tensor, s: StencilVector, p: StencilVector, p_next: StencilVector,
+                   q: StencilVector) -> torch.Tensor:
+        """pcg's p update inside the apply + dot that follows it, one launch
+        (``poms_op_papply_dot``): ``p_next = s + beta p``, ``q = A p_next`` and ``p_next . q``
+        (a device tensor of shape (1,)); ``beta``: a device float64 tensor of one element.
+        Only the interior of ``p_next`` is written: its ghosts must be zero already."""
+        self._check(s, p, p_next, q)
+        out = torch.zeros(1, dtype=F64, device=beta.device)
+        _lib.call("poms_op_papply_dot", self._h, rt.ptr(beta), rt.ptr(s._data), rt.ptr(p._data), rt.ptr(p_next._data),
+                  rt.ptr(q._data), rt.ptr(out), _stream())
+        p_next._mark_written()
+        q._mark_written()
+        return out
+
+    @property
+    def papply_dot_count(self) -> int:
+        """Launches of :meth:`papply_dot`'s kernel so far, the native pcg loop's included."""
+        v = C.c_int64()
+        _lib.call("poms_op_papply_dot_count", self._h, C.byref(v))
+        return v.value
+
     def residual(self, b: StencilVector, x: StencilVector, out: StencilVector | None = None) -> StencilVector:
         """r = b - A x, fused (`sources/solvers.py:85`, `sources/mg_jac.py:93`)."""
         self._check(b, x)
