@@ -110,13 +110,6 @@ static bool v5_aligned(const poms_op* o, const double* x) {
     return pitch % 16 == 0 && (reinterpret_cast<uintptr_t>(x + o->L.pads[2]) & 127) == 0;
 }
 
-// axis 1 and axis 2 share their Toeplitz rows bitwise (v5's SAME12 builds)
-static bool same_toeplitz12(const poms_op* o) {
-    for (int k = 0; k <= o->pmax; ++k)
-        if (o->tc.t1a[k] != o->tc.t2a[k] || o->tc.t1b[k] != o->tc.t2b[k]) return false;
-    return true;
-}
-
 // The launch geometry of kernel variant v (v5_to: v5's output columns per tile) for the
 // request's planes.
 static int op_geom(poms_op* o, const OpLaunch& q, KronGeom& g, int v, int v5_to) {
@@ -130,7 +123,7 @@ static int op_geom(poms_op* o, const OpLaunch& q, KronGeom& g, int v, int v5_to)
     g.pd0 = r.pd0; g.pd1 = r.pd1; g.pd2 = r.pd2;
     g.g0 = (int)o->g0;
     g.tiles2 = (int)((o->L.n[2] + kron_tile_cols() - 1) / kron_tile_cols());
-    const int trows = v == 10 ? kron_v5_rows(o->pmax, epi, same_toeplitz12(o) ? 1 : 0)
+    const int trows = v == 10 ? kron_v5_rows(o->pmax, epi, same_toeplitz12(o->tc, o->pmax) ? 1 : 0)
                     : (!is3d && v == 9 && o->pmax == 3) ? kron_v3_rows_2d() : kron_tile_rows();
     g.tiles1 = (int)((o->L.n[1] + trows - 1) / trows);
     g.tout = v == 10 ? v5_to : (o->tout > 0 ? o->tout : 64 - 2 * o->pmax);
@@ -181,7 +174,7 @@ static int op_geom(poms_op* o, const OpLaunch& q, KronGeom& g, int v, int v5_to)
         // 865-882 us in two interleaved sweeps, equal medians (833 us) in a third
         // (profiles/r03/chunks/); the other epilogues keep the model's pick (Jacobi
         // 715 us at 172 against 729 at 86)
-        if (!one && v == 10 && epi == EPI_JACOBI0 && o->pmax == 3 && same_toeplitz12(o) && chunk / 2 >= 8 * o->pmax)
+        if (!one && v == 10 && epi == EPI_JACOBI0 && o->pmax == 3 && same_toeplitz12(o->tc, o->pmax) && chunk / 2 >= 8 * o->pmax)
             chunk = (chunk + 1) / 2;   // (the 16-wave build only)
     }
     chunk = std::max(1, std::min(chunk, std::max(nz, 1)));

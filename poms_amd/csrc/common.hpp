@@ -40,7 +40,7 @@ struct KronGeom {
 };
 
 // Output planes [z0, z1) of axis-0 chunk `ch` (3D launches may cover two ranges).
-__device__ __forceinline__ void chunk_planes(const KronGeom& g, int ch, int& z0, int& z1) {
+__host__ __device__ __forceinline__ void chunk_planes(const KronGeom& g, int ch, int& z0, int& z1) {
     if (ch < g.nch1) {
         z0 = g.z_begin + ch * g.chunk;
         z1 = min(z0 + g.chunk, g.z_end);
@@ -189,6 +189,14 @@ struct ToepConst {
     int lo1, hi1, lo0, hi0, lo2, hi2;
     double rdi;              // 1/diag(A) inside the Toeplitz interior of every axis (3D; 0 if empty)
 };
+
+// Axes 1 and 2 share their Toeplitz rows bitwise (one knot vector on both axes): v5's
+// SAME12 builds, its tile height and its chunking all ask this.
+inline bool same_toeplitz12(const ToepConst& tc, int P) {
+    for (int k = 0; k <= P; ++k)
+        if (tc.t1a[k] != tc.t2a[k] || tc.t1b[k] != tc.t2b[k]) return false;
+    return true;
+}
 
 // Device pointers of one fused Kronecker launch.
 struct KronPtrs {

@@ -35,27 +35,13 @@
 // array < 2 GiB.
 #include "common.hpp"
 #include "launchers.hpp"
+#include "wave_ops.hpp"
 
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
 namespace poms {
-
-namespace {
-__device__ __forceinline__ double j2_shr1(double v) {   // lane l <- lane l-1 (lane 0 <- 0)
-    const int2 w = __builtin_bit_cast(int2, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, w.x, 0x138, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, w.y, 0x138, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, make_int2(lo, hi));
-}
-__device__ __forceinline__ double j2_shl1(double v) {   // lane l <- lane l+1 (lane 63 <- 0)
-    const int2 w = __builtin_bit_cast(int2, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, w.x, 0x130, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, w.y, 0x130, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, make_int2(lo, hi));
-}
-}  // namespace
 
 constexpr int kJ2Waves = 8;
 constexpr int kJ2Rows = 6;       // output rows of waves 1..6
@@ -135,8 +121,8 @@ kron2d_j2_kernel(const double* __restrict__ x, double* __restrict__ y, const dou
         sh[P] = v;
 #pragma unroll
         for (int d = 1; d <= P; ++d) {
-            sh[P - d] = j2_shr1(sh[P - d + 1]);
-            sh[P + d] = j2_shl1(sh[P + d - 1]);
+            sh[P - d] = shr1(sh[P - d + 1]);
+            sh[P + d] = shl1(sh[P + d - 1]);
         }
         double ca, cb;
         c2(0, ca, cb);

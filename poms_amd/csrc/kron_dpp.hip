@@ -18,24 +18,12 @@
 // Preconditions: storage pads == P on every used axis (checked by the host).
 #include "common.hpp"
 #include "launchers.hpp"
+#include "wave_ops.hpp"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace poms {
-
-__device__ __forceinline__ double dpp_shr1(double v) {  // lane l <- lane l-1 (lane 0 <- 0)
-    const int2 w = __builtin_bit_cast(int2, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, w.x, 0x138, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, w.y, 0x138, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, make_int2(lo, hi));
-}
-__device__ __forceinline__ double dpp_shl1(double v) {  // lane l <- lane l+1 (lane 63 <- 0)
-    const int2 w = __builtin_bit_cast(int2, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, w.x, 0x130, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, w.y, 0x130, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, make_int2(lo, hi));
-}
 
 template <int P, int R, int NW, bool IS3D, int FORM, int EPI, int PF, int MODE = 0, bool FLAT = false>
 __global__ void __launch_bounds__(NW * 64, ((P <= 3 && NW <= 8 ? 2 : 1) * NW * 64) / 256)  // 16 waves/CU for P <= 3
@@ -339,8 +327,8 @@ kron_v3_kernel(const double* __restrict__ x, double* __restrict__ y,
                     }
 #pragma unroll
                     for (int d = 1; d <= P; ++d) {
-                        sh[P - d] = dpp_shr1(sh[P - d + 1]);  // column i2 - d
-                        sh[P + d] = dpp_shl1(sh[P + d - 1]);  // column i2 + d
+                        sh[P - d] = shr1(sh[P - d + 1]);  // column i2 - d
+                        sh[P + d] = shl1(sh[P + d - 1]);  // column i2 + d
                     }
                     double sa, sb = 0.0;
                     if constexpr (MODE == 1) {

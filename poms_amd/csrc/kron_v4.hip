@@ -24,6 +24,7 @@
 // Preconditions (checked by the host): storage pads == P on every used axis.
 #include "common.hpp"
 #include "launchers.hpp"
+#include "wave_ops.hpp"
 
 namespace poms {
 
@@ -31,26 +32,6 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, double* lds_dst, int voff) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_t*)lds_dst, 16, voff, 0, 0, 0);
-}
-
-__device__ __forceinline__ double v4_shr1(double v) {  // lane l <- lane l-1
-    const int2 w = __builtin_bit_cast(int2, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, w.x, 0x138, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, w.y, 0x138, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, make_int2(lo, hi));
-}
-__device__ __forceinline__ double v4_shl1(double v) {  // lane l <- lane l+1
-    const int2 w = __builtin_bit_cast(int2, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, w.x, 0x130, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, w.y, 0x130, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, make_int2(lo, hi));
-}
-
-// s_waitcnt vmcnt(N) only (gfx9 encoding: vmcnt[3:0], expcnt[6:4], lgkmcnt[11:8], vmcnt[5:4] at [15:14])
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
 }
 
 template <int P, int NW, bool IS3D, int FORM, int EPI, int MODE = 0, bool EXDPP = true, int MINW = (2 * NW * 64) / 256, int DFORCE = 0>
@@ -298,9 +279,9 @@ kron_v4_kernel(const double* __restrict__ x, double* __restrict__ y,
                         win[P] = f0;
                         win[P + 1] = f1;
 #pragma unroll
-                        for (int i = P - 1; i >= 0; --i) win[i] = v4_shr1(win[i + 2]);
+                        for (int i = P - 1; i >= 0; --i) win[i] = shr1(win[i + 2]);
 #pragma unroll
-                        for (int i = P + 2; i <= 2 * P + 1; ++i) win[i] = v4_shl1(win[i - 2]);
+                        for (int i = P + 2; i <= 2 * P + 1; ++i) win[i] = shl1(win[i - 2]);
                         return;
                     }
                     __builtin_amdgcn_wave_barrier();

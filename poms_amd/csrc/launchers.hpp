@@ -10,6 +10,9 @@
 namespace poms {
 
 // ---- kron_fused.hip (v0), kron_dpp.hip (v3), kron_v4.hip, kron_v5.hip, kron_2d.hip ----
+// (v5: kron_v5.hip is the host side; its kernel builds are compiled by kron_v5_p1.hip ..
+// kron_v5_p5.hip and kron_v5_diag.hip from kron_v5_kernel.hpp, which declares those units'
+// entries; kron_v5_stamps is defined in kron_v5_diag.hip beside the stamp buffer)
 int kron_launch(int pmax, bool is3d, int form, int epi, const KronPtrs& p, const KronGeom& g,
                 double omega, hipStream_t st);
 int kron_tile_rows();

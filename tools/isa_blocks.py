@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-basic-block instruction classes of one kernel in a device .s file.
 
-    hipcc --offload-arch=gfx950 -O3 --cuda-device-only -S kron_v5.hip -o v5.s
+    hipcc --offload-arch=gfx950 -O3 --cuda-device-only -S kron_v5_p3.hip -o v5.s
     python tools/isa_blocks.py v5.s <kernel-name-substring> [--body]
 
 Prints, per block: label, instruction count, VALU (of which FP64, DPP, readlane /

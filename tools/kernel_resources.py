@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Register / scratch use of every kernel in a built object's device code.
 
-    python tools/kernel_resources.py poms_amd/_obj/kron_v5.hip.o [name-substring ...]
+    python tools/kernel_resources.py poms_amd/_obj/kron_v5_p3.hip.o [name-substring ...]
 
 Extracts the gfx950 code object from the object's .hip_fatbin section
 (llvm-objcopy + clang-offload-bundler) and reads the AMDHSA metadata notes:

@@ -1,9 +1,10 @@
 #!/bin/bash
-# VGPR count and scratch bytes of every kron_v5_kernel build in poms_amd/_obj/kron_v5.hip.o
+# VGPR count and scratch bytes of every kron_v5_kernel build in one unit's object (default: the p = 3
+# production builds, poms_amd/_obj/kron_v5_p3.hip.o; the others: kron_v5_p<P>.hip.o, kron_v5_diag.hip.o)
 # (CPU-side check before a GPU run: a build with scratch would make the v5 launch refuse)
 set -eu
 T=$(mktemp -d)
-/opt/rocm/lib/llvm/bin/llvm-objcopy --dump-section .hip_fatbin=$T/fb.bin "${1:-poms_amd/_obj/kron_v5.hip.o}" $T/host.o
+/opt/rocm/lib/llvm/bin/llvm-objcopy --dump-section .hip_fatbin=$T/fb.bin "${1:-poms_amd/_obj/kron_v5_p3.hip.o}" $T/host.o
 /opt/rocm/lib/llvm/bin/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 \
     --input=$T/fb.bin --output=$T/dev.o --unbundle
 /opt/rocm/lib/llvm/bin/llvm-readelf --notes $T/dev.o | python3 -c '
