@@ -33,11 +33,12 @@
 extern "C" {
 #endif
 
-#define POMS_ABI_VERSION 10 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
+#define POMS_ABI_VERSION 11 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
                              * 7: poms_pcg_opts.n_pbuf, .pbuf;
                              * 8: poms_op_set_dirichlet, poms_op_get_dirichlet;
                              * 9: poms_op_cheby_step, poms_op_cheby_supported;
-                             * 10: poms_op_papply_dot (+ _supported, _count), poms_pcg_p_update_dev */
+                             * 10: poms_op_papply_dot (+ _supported, _count), poms_pcg_p_update_dev;
+                             * 11: poms_op_add_face_term, poms_op_face_terms */
 
 /* operator forms (see poms_op_create) */
 #define POMS_FORM_SINGLE 0 /* y = F0 (x) F1 (x) F2 x                                  */
@@ -701,6 +702,32 @@ int poms_op_spec_stats(poms_op* op, int* stats);
  * caller must not change the mask between capture and replay.                          */
 int poms_op_set_dirichlet(poms_op* op, int faces);
 int poms_op_get_dirichlet(poms_op* op, int* faces);
+/* (ABI 11) Natural boundary terms on whole faces of a general-stencil or matrix-free operator:
+ * the face mass S_ij = int_Gamma beta phi_i phi_j ds of a Robin condition
+ * (G grad u) . n + beta u = g on the face (axis, side) (the operator's own axes; side 0: index
+ * 0, side 1: index n_axis - 1).  On open knot vectors only the boundary layer of coefficients
+ * is non-zero on the face, so S couples the rows of that layer among themselves and is a
+ * (d-1)-dimensional stencil: `coef_host` holds it as [m_a][m_b][2 half_a + 1][2 half_b + 1]
+ * doubles over the face's two axes in increasing order of the kernels' three axes (a 2D
+ * operator's unused leading axis counts: m_a = 1, half_a = 0), C order, couplings to columns
+ * outside the grid zero.  `m` and `half` (two entries each) must equal the operator's extents
+ * and half-widths on those axes.  The operator becomes A + S: a stored stencil adds S into
+ * the coefficients of the boundary plane's rows at the offsets (k_a, centre, k_b), so
+ * poms_op_diagonal, poms_op_stencil_data, poms_op_galerkin_stencil and the Dirichlet mask all
+ * see A + S; a matrix-free operator keeps a device copy per face, adds the centres into its
+ * stored diagonal and applies the term in its kernel where an output plane is final
+ * (neighbours outside the grid skipped; under a Dirichlet mask neighbours on a constrained
+ * face skipped and constrained rows diag * x with the updated diagonal).  Calling it twice
+ * for one face adds twice.  A set-up call on the null stream, ending in a device
+ * synchronise; captured graphs of poms_pcg_jacobi are re-keyed.  Refused, before any
+ * launch: null arguments, an axis or side out of range, m / half that do not match,
+ * Kronecker forms, slabs and Cart blocks, and a call during a stream capture (as far as the
+ * call can see one: poms_op_set_dirichlet's test).
+ * poms_op_face_terms: the bitmask (bit 2 axis + side, the operator's axes) of the faces that
+ * carry a term.                                                                          */
+int poms_op_add_face_term(poms_op* op, int axis, int side, const double* coef_host, const int64_t* m,
+                          const int* half);
+int poms_op_face_terms(poms_op* op, int* faces);
 int poms_op_timing_read(poms_op* op, int epilogue, double* total_ms, int64_t* launches, int64_t* dofs);
 
 /* ---- spline fields on tensor point grids --------------------------------------- */

@@ -25,7 +25,7 @@ __all__ = [
     "galerkin_stencil", "GalerkinVCycle",
     "MatrixFreeOperator", "MatrixFreeVCycle",
     "Mapping", "SplineMapping", "MappedDomain", "pullback",
-    "DirichletBC",
+    "DirichletBC", "RobinBC",
 ]
 
 
@@ -67,9 +67,9 @@ def __getattr__(name):
     if name in ("Mapping", "SplineMapping", "MappedDomain", "pullback"):
         from . import geometry
         return getattr(geometry, name)
-    if name == "DirichletBC":
-        from .boundary import DirichletBC
-        return DirichletBC
+    if name in ("DirichletBC", "RobinBC"):
+        from . import boundary
+        return getattr(boundary, name)
     if name == "SlabDistribution":
         from .dist import SlabDistribution
         return SlabDistribution

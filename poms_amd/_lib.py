@@ -90,6 +90,8 @@ _SIGS = {
     "poms_op_spec_stats": [_vp, C.POINTER(_i)],
     "poms_op_set_dirichlet": [_vp, _i],
     "poms_op_get_dirichlet": [_vp, C.POINTER(_i)],
+    "poms_op_add_face_term": [_vp, _i, _i, _vp, C.POINTER(_i64), C.POINTER(_i)],
+    "poms_op_face_terms": [_vp, C.POINTER(_i)],
     "poms_vec_axpby_dev": [_vp, _LP, _vp, _vp, _vp, _vp, _vp],
     "poms_op_run_reduce": [_vp, _i, _d, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i, _vp],
     "poms_op_run_reduce2": [_vp, _i, _d, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i, _vp],

@@ -214,7 +214,7 @@ def quadrature_args(V: StencilVectorSpace, knots, nquad: int | None = None):
 
 
 def assemble_stencil(V: StencilVectorSpace, knots, a=None, c=None, mass_coef: float = 1.0,
-                     nquad: int | None = None, dirichlet=None) -> StencilMatrix:
+                     nquad: int | None = None, dirichlet=None, robin=None) -> StencilMatrix:
     """``-∇·(a ∇u) + c u`` on the tensor space of ``knots`` (one knot vector per axis,
     degree = the space's pads), assembled on the device.  ``a``/``c``: None (1 and
     ``mass_coef``), a callable of the quadrature-point coordinates (``meshgrid``,
@@ -222,8 +222,14 @@ def assemble_stencil(V: StencilVectorSpace, knots, a=None, c=None, mass_coef: fl
     tensor coefficient: an array, a float64 device tensor, or a callable returning
     either, of shape ``(ncomp,) + quad_shape`` (see the module's text).  ``dirichlet``:
     constrained faces, passed to ``set_dirichlet`` (the assembled coefficients are those
-    of the unconstrained operator)."""
+    of the unconstrained operator).  ``robin``: ``{(axis, side): β}`` or a
+    :class:`~poms_amd.boundary.RobinBC` of this space (which knows a mapping): the face
+    masses are added into the stored coefficients, which are then those of ``A + S``."""
     nd = V.ndim
+    if robin is not None:   # (refused before anything is assembled)
+        from .boundary import RobinBC
+        if not isinstance(robin, RobinBC):
+            robin = RobinBC(V, knots, robin, nquad=nquad)
     if dirichlet is not None:   # (refused before anything is assembled)
         from .boundary import normalize_faces
         if normalize_faces(dirichlet, nd) is not None and (V.is_distributed or V.is_cart):
@@ -243,6 +249,8 @@ def assemble_stencil(V: StencilVectorSpace, knots, a=None, c=None, mass_coef: fl
         _lib.call("poms_op_assemble_stencil", V.ctx, nd, C.byref(V.layout), *tables,
                   None if aq is None else C.c_void_p(aq.data_ptr()), *tail)
     A = StencilMatrix._from_handle(V, h)
+    if robin is not None:
+        robin.apply(A)
     if dirichlet is not None:
         A.set_dirichlet(dirichlet)
     return A

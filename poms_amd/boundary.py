@@ -17,6 +17,12 @@ constrained set C holds every coefficient whose index is 0 on an axis with ``lo`
   right-hand side ``Π (b − A xg)``; the solution is ``xg + x`` with ``A_D x`` = that.
 
 This module is the one place that reads the spellings of ``faces``.
+
+Natural conditions with data live here too (:class:`RobinBC`): on a face ``(axis, side)``
+the condition ``(G∇u)·n + β u = g`` adds the face mass ``S_ij = ∫_Γ β φ_i φ_j ds`` to the
+operator and the face load ``∫_Γ g φ_i ds`` to the right-hand side (``β = 0``: inhomogeneous
+Neumann, the right-hand side only).  Both are (d−1)-dimensional objects on the boundary layer
+of coefficients, because on open knots the end function is 1 on the face and the others 0.
 """
 from __future__ import annotations
 
@@ -27,7 +33,8 @@ import numpy as np
 from .splines import basis_funs_ders, find_span, greville
 
 __all__ = ["normalize_faces", "faces_mask", "mask_faces", "constrained_mask", "constrain_dense",
-           "check_unit_rows", "constrain_prolongation", "collocation_1d", "lift_host", "DirichletBC"]
+           "check_unit_rows", "constrain_prolongation", "collocation_1d", "lift_host", "DirichletBC",
+           "normalize_robin", "add_face_term", "RobinBC"]
 
 
 def normalize_faces(faces, ndim: int):
@@ -240,3 +247,223 @@ class DirichletBC:
             if faces is not None:
                 A.set_dirichlet(faces)
         return self.project(r)
+
+
+def normalize_robin(robin, ndim: int) -> dict:
+    """``{(axis, side): value}`` with the faces in the order axis 0 lo, axis 0 hi, axis 1 lo, …
+    (``side`` 0: index 0, 1: index ``n_axis − 1``, the numbering of ``poms_op_set_dirichlet``'s
+    bits); None or an empty dict gives ``{}``."""
+    if robin is None:
+        return {}
+    if not isinstance(robin, dict):
+        raise ValueError(f"robin: expected a dict {{(axis, side): value}}, got {type(robin).__name__}")
+    out = {}
+    for key, val in robin.items():
+        try:
+            axis, side = key
+        except (TypeError, ValueError):
+            raise ValueError(f"robin: a face is an (axis, side) pair, got {key!r}") from None
+        if not (isinstance(axis, (int, np.integer)) and 0 <= axis < ndim) or side not in (0, 1):
+            raise ValueError(f"robin: face {key!r}: axis must be 0 .. {ndim - 1} and side 0 or 1")
+        out[(int(axis), int(side))] = val
+    return dict(sorted(out.items()))
+
+
+def add_face_term(A, face, S: np.ndarray) -> None:
+    """Add the face stencil ``S`` (:meth:`RobinBC.mass`) of ``face`` to a general form
+    (``poms_op_add_face_term``): a stored stencil takes it into its coefficients, a
+    matrix-free operator keeps it beside its quadrature form.  Host copies of what changed
+    (the stencil's ``_data``, the matrix-free diagonal, the Chebyshev bound) are dropped."""
+    import ctypes as C
+
+    from . import _lib
+    if getattr(A, "form", None) not in ("stencil", "matfree"):
+        raise NotImplementedError("robin: a Kronecker operator takes its face terms through its factors: build it "
+                                  "with KronOperator.laplace(..., robin=)")
+    axis, side = face
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    if S.ndim != 4:
+        raise ValueError(f"robin: a face stencil has four dimensions (m_a, m_b, 2p_a+1, 2p_b+1), got shape {S.shape}")
+    h = A._h   # (a stencil edited on the host is uploaded first)
+    m = (C.c_int64 * 2)(S.shape[0], S.shape[1])
+    half = (C.c_int * 2)((S.shape[2] - 1) // 2, (S.shape[3] - 1) // 2)
+    try:
+        _lib.call("poms_op_add_face_term", h, int(axis), int(side), S.ctypes.data_as(C.c_void_p), m, half)
+    except _lib.PomsError as e:
+        raise ValueError(str(e)) from None
+    if A.form == "stencil":
+        A._host = None   # (fetched again from the device on the next host-side access)
+    else:
+        A._diag = None
+    A._lmax_est = None
+    A._face_terms.append(((int(axis), int(side)), S))
+
+
+class RobinBC:
+    """Robin and inhomogeneous Neumann conditions ``(G∇u)·n + β u = g`` on whole faces of the
+    space ``V`` of ``knots``.
+
+    ``robin``: ``{(axis, side): β}``, ``β`` a scalar or a NumPy callable of the face's
+    ``meshgrid`` coordinates (``indexing='ij'``): the d−1 parameter coordinates of the face's
+    axes, or the d physical coordinates when a ``mapping`` of :mod:`poms_amd.geometry` is
+    given.  The face terms are integrated with ``nquad`` Gauss points per element (default
+    ``p+1``) times the surface Jacobian of the mapping (1 without one)."""
+
+    def __init__(self, V, knots, robin, mapping=None, nquad: int | None = None):
+        from .assembly import axis_tables
+        if len(knots) != V.ndim:
+            raise ValueError(f"{V.ndim}D space needs {V.ndim} knot vectors")
+        if V.ndim not in (2, 3):
+            raise ValueError("robin: face terms are implemented for 2D and 3D spaces")
+        if V.is_distributed or V.is_cart or tuple(V.local_npts) != tuple(V.npts):
+            raise NotImplementedError("robin: distributed (slab / Cart) spaces are not supported")
+        self.space, self.mapping, self.nquad = V, mapping, nquad
+        self.knots = [np.asarray(T, dtype=np.float64) for T in knots]
+        self.robin = normalize_robin(robin, V.ndim)
+        self._tabs = [axis_tables(T, V.pads[d], nquad) for d, T in enumerate(self.knots)]
+        self._dev = f"cuda:{V.device}"
+        self._quad = {}   # per normal axis: the face space and its QuadGrid (3D)
+
+    def _face(self, face):
+        (axis, side), = normalize_robin({face: 0.0}, self.space.ndim)
+        return axis, side
+
+    def face_points(self, face):
+        """Per-axis 1D point arrays of the face's quadrature grid: the Gauss points on the
+        face's axes, the single end point on the normal axis."""
+        axis, side = self._face(face)
+        T, p = self.knots[axis], self.space.pads[axis]
+        end = T[p] if side == 0 else T[len(T) - p - 1]
+        return [np.array([end]) if d == axis else t["points"].reshape(-1) for d, t in enumerate(self._tabs)]
+
+    def _surface(self, face):
+        """The surface Jacobian on the face's quadrature grid (device tensor), or None for 1."""
+        if self.mapping is None:
+            return None
+        from .geometry import surface_measure
+        axis, _ = self._face(face)
+        return surface_measure(self.mapping.jacobian(self.face_points(face), self._dev), axis).squeeze(axis).contiguous()
+
+    def _weights(self, face) -> np.ndarray:
+        axis, _ = self._face(face)
+        w = np.ones(())
+        for d, t in enumerate(self._tabs):
+            if d != axis:
+                w = np.multiply.outer(w, t["weights"].reshape(-1))
+        return w
+
+    def measure(self, face, weights: bool = True):
+        """``w·ds`` on the face's quadrature grid (its d−1 axes in increasing order): the Gauss
+        weights of the face's axes times the surface Jacobian, a device tensor.  Every face
+        integral of this class is a sum over it.  ``weights=False``: ``ds`` alone, for the
+        device paths whose kernels apply the Gauss weights themselves."""
+        import torch
+        ds = self._surface(face)
+        if not weights:
+            shape = tuple(len(q) for d, q in enumerate(self.face_points(face)) if d != self._face(face)[0])
+            return torch.ones(shape, dtype=torch.float64, device=self._dev) if ds is None else ds
+        w = torch.from_numpy(np.ascontiguousarray(self._weights(face))).to(self._dev)
+        return w if ds is None else w * ds
+
+    def _sample(self, face, f) -> np.ndarray:
+        """``f`` on the face's quadrature grid: a scalar, or a callable of the d−1 parameter
+        coordinates of the face (of the d physical coordinates under a mapping)."""
+        axis, _ = self._face(face)
+        pts = self.face_points(face)
+        shape = tuple(len(q) for d, q in enumerate(pts) if d != axis)
+        if not callable(f):
+            if np.ndim(f) != 0:
+                raise ValueError("robin: β and g are scalars or callables of the face's coordinates")
+            return np.full(shape, float(f))
+        if self.mapping is None:
+            coords = np.meshgrid(*[q for d, q in enumerate(pts) if d != axis], indexing="ij")
+        else:
+            coords = [np.squeeze(x.cpu().numpy(), axis=axis) for x in self.mapping.physical(pts, self._dev)]
+        return np.array(np.broadcast_to(np.asarray(f(*coords), dtype=np.float64), shape), order="C")
+
+    def _face_space(self, face):
+        """The 2D space of a 3D problem's face and its quadrature grid (shared by both sides)."""
+        from .field import QuadGrid
+        from .stencil import StencilVectorSpace
+        axis, _ = self._face(face)
+        if axis not in self._quad:
+            V = self.space
+            ax = [d for d in range(V.ndim) if d != axis]
+            Vf = StencilVectorSpace([V.npts[d] for d in ax], [V.pads[d] for d in ax], device=V.device)
+            kn = [self.knots[d] for d in ax]
+            self._quad[axis] = (Vf, kn, QuadGrid(Vf, kn, self.nquad))
+        return self._quad[axis]
+
+    def _weighted(self, face, f) -> np.ndarray:
+        """``f`` times :meth:`measure` on the face's quadrature grid, on the host: ``f w ds`` for
+        the 1D face of a 2D problem, summed on the host; ``f ds`` in 3D, where
+        ``assemble_stencil`` and ``QuadGrid.load_vector`` on the face space apply ``w``."""
+        return self._sample(face, f) * self.measure(face, weights=self.space.ndim == 2).cpu().numpy()
+
+    def mass(self, face, beta=None) -> np.ndarray:
+        """The face stencil ``S[i_a, i_b, k_a, k_b] = ∫_Γ β φ_i φ_(i+k−p) ds`` over the face's two
+        axes in increasing order: float64 ``(m_a, m_b, 2p_a+1, 2p_b+1)``, interior rows only, C
+        order, couplings to columns outside the grid exact zeros; a 2D operator has ``m_a = 1``,
+        ``p_a = 0``.  In 3D it is :func:`~poms_amd.assembly.assemble_stencil` on the 2D face
+        space with ``a = 0``, ``c = β ds``; the 1D face of a 2D problem is formed on the host
+        from :func:`~poms_amd.assembly.axis_tables`.  ``beta``: default the face's own."""
+        axis, side = self._face(face)
+        if beta is None:
+            beta = self.robin[(axis, side)]
+        c = self._weighted((axis, side), beta)
+        if self.space.ndim == 3:
+            from .assembly import assemble_stencil
+            Vf, kn, _ = self._face_space((axis, side))
+            Sf = assemble_stencil(Vf, kn, a=0.0, c=c, nquad=self.nquad)
+            return np.ascontiguousarray(Sf._data[tuple(slice(p, p + n) for p, n in zip(Vf.pads, Vf.npts))])
+        t = self._tabs[1 - axis]
+        p, n, nq = t["p"], t["n"], t["nq"]
+        cw = c.reshape(t["nel"], nq)                         # β w ds
+        S = np.zeros((1, n, 1, 2 * p + 1))
+        for e in range(t["nel"]):
+            B = t["basis"][e, :, :, 0]                       # (nq, p+1)
+            El = np.einsum("q,qi,qj->ij", cw[e], B, B)       # the element's (p+1) x (p+1) block
+            f0 = int(t["first"][e])
+            for li in range(p + 1):
+                S[0, f0 + li, 0, p - li:2 * p + 1 - li] += El[li]
+        return S
+
+    def apply(self, A):
+        """Add every face's term to a :class:`~poms_amd.stencil.StencilMatrix` or a
+        :class:`~poms_amd.matfree.MatrixFreeOperator` on this space: ``A`` becomes ``A + S``
+        (calling it twice adds twice).  Returns ``A``."""
+        if tuple(A.space.npts) != tuple(self.space.npts) or tuple(A.space.pads) != tuple(self.space.pads):
+            raise ValueError("robin: the operator does not live on this space")
+        for face in self.robin:
+            add_face_term(A, face, self.mass(face))
+        return A
+
+    def load_vector(self, g, out=None):
+        """Add the face loads ``∫_Γ g φ_i ds`` into ``out`` (default: a zero vector).  ``g``:
+        ``{(axis, side): data}``, each a scalar or a callable as ``β``; it may name faces that
+        are absent from ``robin`` (pure Neumann faces).  The loads are added into the boundary
+        planes of ``out``, views of its interior (elementwise torch: a set-up path)."""
+        import torch
+        V = self.space
+        g = normalize_robin(g, V.ndim)
+        if out is None:
+            out = V.zeros()
+        inner = V.interior(out._data)
+        for (axis, side), gf in g.items():
+            v = self._weighted((axis, side), gf)
+            if V.ndim == 3:
+                Vf, _, quad = self._face_space((axis, side))
+                load = Vf.interior(quad.load_vector(v)._data)
+            else:
+                t = self._tabs[1 - axis]
+                vw = v.reshape(t["nel"], t["nq"])            # g w ds
+                host = np.zeros(t["n"])
+                for e in range(t["nel"]):
+                    f0 = int(t["first"][e])
+                    host[f0:f0 + t["p"] + 1] += vw[e] @ t["basis"][e, :, :, 0]
+                load = torch.from_numpy(host).to(self._dev)
+            idx = [slice(None)] * V.ndim
+            idx[axis] = 0 if side == 0 else V.npts[axis] - 1
+            inner[tuple(idx)] += load
+        out._mark_written()
+        return out

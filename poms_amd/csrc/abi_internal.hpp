@@ -88,6 +88,12 @@ struct poms_op {
     double mf_mass = 1.0;
     poms::MatfreeGeom mf_geom{};
     int dmask = 0;      // general forms: Dirichlet faces in the kernels' axes (poms_op_set_dirichlet)
+    // general forms: the faces that carry a term (poms_op_add_face_term), in the kernels' axes.
+    // FORM_STENCIL holds the terms in `coef`; FORM_MATFREE keeps each face's stencil (host sum of
+    // every call, and its device copy in mf_faces, owned) and has the centres in mf_diag
+    int fmask = 0;
+    std::vector<double> mf_face_host[6];
+    poms::MatfreeFaces mf_faces{};
     uint64_t gen = 0;  // bumped by every setter that changes the launches a graph would capture
     // op_run_split's interior launch: the communication stream's exchange and boundary
     // launch run beside it (the automatic chunking leaves them CUs, op_geom); written

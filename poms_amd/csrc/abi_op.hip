@@ -244,7 +244,7 @@ static int matfree_run(poms_op* o, const OpLaunch& q) {
     const bool wd = want_dot || epi == EPI_APPLYDOT;
     if (matfree_launch(epi, g, o->mf_ax, q.x, q.y, q.b, o->mf_a, o->mf_c, o->mf_diag, o->mf_mass, q.omega,
                        want_norm ? scr : nullptr, wd ? scr + nblk : nullptr, maxb, as_stream(q.stream), &nb,
-                       o->mf_tensor, q.beta))
+                       o->mf_tensor, q.beta, &o->mf_faces))
         return 1;
     POMS_HIP_CHECK(hipGetLastError());
     o->last_partials = (want_norm || wd) ? nb : 0;
@@ -672,6 +672,18 @@ int poms_op_spec_stats(poms_op* op, int* stats) {
     return 0;
 }
 
+// A stream capture is in progress, as far as a call without a stream argument can see one:
+// the legacy stream answers for a capture on any stream of the thread in the global capture
+// mode; the operator's own capture stream is asked as well.
+static bool capture_in_progress(const poms_op* op) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    bool capturing = hipStreamIsCapturing(nullptr, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    if (!capturing && op->cap_stream)
+        capturing = hipStreamIsCapturing(op->cap_stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    if (capturing) (void)hipGetLastError();
+    return capturing;
+}
+
 // Dirichlet faces of a general form.  The mask is a run-time field of the launch
 // geometry; bumping `gen` re-keys the captured graphs of poms_pcg_jacobi (nothing else the
 // operator caches depends on what a launch computes).
@@ -691,17 +703,7 @@ int poms_op_set_dirichlet(poms_op* op, int faces) {
         set_error(fn + "distributed operators (slabs, Cart blocks) are not supported");
         return 1;
     }
-    // (the legacy stream answers for a capture in progress on any stream of the thread
-    // in the global capture mode; the operator's own capture stream is asked as well)
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    bool capturing = hipStreamIsCapturing(nullptr, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-    if (!capturing && op->cap_stream)
-        capturing = hipStreamIsCapturing(op->cap_stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-    if (capturing) {
-        (void)hipGetLastError();
-        set_error(fn + "called during a stream capture");
-        return 1;
-    }
+    if (capture_in_progress(op)) { set_error(fn + "called during a stream capture"); return 1; }
     const int m = faces << (2 * (3 - op->ndim));   // the operator's axes are the kernels' last ndim
     if (m == op->dmask) return 0;
     op->dmask = m;
@@ -713,6 +715,81 @@ int poms_op_set_dirichlet(poms_op* op, int faces) {
 int poms_op_get_dirichlet(poms_op* op, int* faces) {
     if (!op || !faces) { set_error("poms_op_get_dirichlet: null argument"); return 1; }
     *faces = op->dmask >> (2 * (3 - op->ndim));
+    return 0;
+}
+
+// A face term of a general form (the face mass of a Robin condition): see the header.  A
+// set-up call: every check comes first, the launch runs on the null stream and the call ends
+// in a device synchronise.
+int poms_op_add_face_term(poms_op* op, int axis, int side, const double* coef_host, const int64_t* m,
+                          const int* half) {
+    const std::string fn = "poms_op_add_face_term: ";
+    if (!op || !coef_host || !m || !half) { set_error(fn + "null argument"); return 1; }
+    if (!general_form(op)) {
+        set_error(fn + "Kronecker forms take a Robin term through their factors (needs a general-stencil or matrix-free operator)");
+        return 1;
+    }
+    if (axis < 0 || axis >= op->ndim) { set_error(fn + "axis must be 0 .. ndim - 1 = " + std::to_string(op->ndim - 1)); return 1; }
+    if (side != 0 && side != 1) { set_error(fn + "side must be 0 or 1"); return 1; }
+    if (distributed(op)) {
+        set_error(fn + "distributed operators (slabs, Cart blocks) are not supported");
+        return 1;
+    }
+    const RowGeom r = row_geom(&op->L);
+    const int ax = axis + (3 - op->ndim);   // the operator's axes are the kernels' last ndim
+    const int a = ax == 0 ? 1 : 0, b = ax == 2 ? 1 : 2;
+    const int n[3] = {r.n0, r.n1, r.n2};
+    if (m[0] != n[a] || m[1] != n[b] || half[0] != op->sp[a] || half[1] != op->sp[b]) {
+        set_error(fn + "m and half must be the operator's extents and half-widths on the face's axes: (" +
+                  std::to_string(n[a]) + ", " + std::to_string(n[b]) + ") and (" + std::to_string(op->sp[a]) + ", " +
+                  std::to_string(op->sp[b]) + ")");
+        return 1;
+    }
+    if (capture_in_progress(op)) { set_error(fn + "called during a stream capture"); return 1; }
+    POMS_HIP_CHECK(hipSetDevice(op->ctx->device));
+    const int f = 2 * ax + side;
+    const size_t len = (size_t)n[a] * n[b] * (2 * op->sp[a] + 1) * (2 * op->sp[b] + 1);
+    const StencilGeom g = stencil_geom(r, op->sp, 0, r.n0, 0, 0, 0);
+    double* d = nullptr;
+    if (upload(coef_host, len, &d)) return 1;
+    // a matrix-free face keeps the sum of every call's stencil, on the host and on the device:
+    // a later call re-uploads the sum first, so that a failed copy leaves the diagonal untouched
+    const bool again = op->form == FORM_MATFREE && !op->mf_face_host[f].empty();
+    std::vector<double> sum;
+    if (again) {
+        sum = op->mf_face_host[f];
+        for (size_t k = 0; k < len; ++k) sum[k] += coef_host[k];
+        if (hipMemcpy(const_cast<double*>(op->mf_faces.s[f]), sum.data(), len * sizeof(double),
+                      hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(d);
+            set_error(fn + "the copy of the face stencil failed");
+            return 1;
+        }
+    }
+    face_add_launch(g, ax, side, d, op->form == FORM_STENCIL ? op->coef : nullptr,
+                    op->form == FORM_MATFREE ? op->mf_diag : nullptr, nullptr);
+    const bool ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (ok && op->form == FORM_MATFREE) {
+        if (again) {
+            op->mf_face_host[f].swap(sum);
+        } else {
+            op->mf_face_host[f].assign(coef_host, coef_host + len);
+            op->mf_faces.s[f] = d;   // (the handle owns it from here)
+            d = nullptr;
+        }
+        op->mf_faces.mask |= 1 << f;
+    }
+    if (d) (void)hipFree(d);
+    if (!ok) { set_error(fn + "the launch failed"); return 1; }
+    op->fmask |= 1 << f;
+    ++op->gen;
+    return 0;
+}
+
+int poms_op_face_terms(poms_op* op, int* faces) {
+    if (!op || !faces) { set_error("poms_op_face_terms: null argument"); return 1; }
+    *faces = op->fmask >> (2 * (3 - op->ndim));
     return 0;
 }
 

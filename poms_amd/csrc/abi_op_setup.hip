@@ -616,6 +616,8 @@ int poms_op_destroy(poms_op* o) {
     for (void* p : o->mf_tabs)
         if (p) (void)hipFree(p);
     if (o->mf_diag) (void)hipFree(o->mf_diag);
+    for (const double* p : o->mf_faces.s)
+        if (p) (void)hipFree(const_cast<double*>(p));
     for (double* p : {o->spec_part, o->spec_host})
         if (p) (void)hipHostFree(p);
     pcg_slots_free(o->sv);

@@ -121,6 +121,14 @@ struct MatfreeGeom {
     int dmask;               // Dirichlet faces, bit 2 axis + side (0: none)
 };
 
+// Face terms of a matrix-free operator (poms_op_add_face_term): per face 2 axis + side, in
+// the kernels' axes, the device copy of its stencil [m_a][m_b][2 p_a + 1][2 p_b + 1] over the
+// face's two axes in increasing order (null: none), and the bitmask of the faces that have one.
+struct MatfreeFaces {
+    const double* s[6];
+    int mask;
+};
+
 // pcg's scalars folded into the flat vector updates (one rank, round 6): every block
 // reduces `n` per-block partials in reduce_partials_kernel's order (the same bits as
 // the one-block kernels they replace) and forms the scalar itself; block 0 stores it.

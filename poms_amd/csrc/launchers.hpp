@@ -80,6 +80,11 @@ int dense_matvec_launch(int n, const double* M, const double* x, double* y, hipS
 int assemble_launch(const AssembleAxis* ax, int g0, int nl0, const double* a_q, const double* c_q, double mass_coef,
                     double* coef, hipStream_t st, int tensor_ndim = 0);
 int stencil_to_spl_launch(const StencilGeom& g, const double* coef, double* out, hipStream_t st);
+// A face stencil [m_a][m_b][2 p_a + 1][2 p_b + 1] (the face's two axes in increasing order) added
+// into the rows of the boundary plane `side` of `axis`: into the coefficient planes `coef` at the
+// offsets (k_a, centre, k_b), or (diag not null) its centres into the dense diagonal `diag`.
+int face_add_launch(const StencilGeom& g, int axis, int side, const double* face, double* coef, double* diag,
+                    hipStream_t st);
 int stencil_launch(int epi, const StencilGeom& g, const double* coef, const double* x, double* y,
                    const double* b, double omega, double* partial, double* partial2, int max_blocks,
                    hipStream_t st, int* nblk_out, double beta = 0.0);   // (beta: EPI_CHEBY only)
@@ -94,7 +99,8 @@ int matfree_diag_launch(const AssembleAxis* ax, const double* a_q, const double*
 int matfree_launch(int epi, const MatfreeGeom& g, const AssembleAxis* ax, const double* x, double* y, const double* b,
                    const double* a_q, const double* c_q, const double* diag, double mass_coef, double omega,
                    double* partial, double* partial2, int max_blocks, hipStream_t st, int* nblk_out,
-                   bool tensor = false, double beta = 0.0);   // (beta: EPI_CHEBY only)
+                   bool tensor = false, double beta = 0.0,    // (beta: EPI_CHEBY only)
+                   const MatfreeFaces* faces = nullptr);     // (face terms: the FACE builds, or null)
 bool matfree_tensor_builds_ok(std::string* why);   // no scratch, at most 256 registers
 
 // ---- stencil_galerkin.hip ---------------------------------------------------------

@@ -67,13 +67,42 @@ int matfree_max_elements() { return MF_E; }
 // blocks moved another hundred scalar reads and writes into vector lanes, 229 / 116 against
 // 136 / 69 in the scalar APPLY build.  The second set of builds adds 4 s to this file's
 // compilation, which runs beside kron_v5.hip's 280 s.)
-template <int EPI, bool TENSOR, bool MASK>
+//
+// FACE builds add the face terms of poms_op_add_face_term (F.mask, bit 2 axis + side; the face
+// mass of a Robin condition) where an output plane is final: a row on such a face adds
+// sum_k S[row, k] x[neighbour] over the face's (d-1)-dimensional stencil, x read from global
+// memory.  As with MASK, FACE only says whether there is a face term, so that an operator
+// without one runs the code it ran before.
+template <int AX, bool MASK>
+__device__ __forceinline__ double face_row(double s, const double* __restrict__ S, const MatfreeGeom& g, int pa, int pb,
+                                           int i0, int i1, int i2, const double* __restrict__ x, int64_t xo) {
+    constexpr int A = AX == 0 ? 1 : 0, B = AX == 2 ? 1 : 2;   // the face's two axes in increasing order
+    const int n[3] = {g.n0, g.n1, g.n2}, i[3] = {i0, i1, i2};
+    const int64_t st[3] = {g.s0, g.s1, 1};
+    const int na = n[A], nb = n[B], ra = i[A], rb = i[B], wb = 2 * pb + 1;
+    const double* Sr = S + ((int64_t)ra * nb + rb) * (2 * pa + 1) * wb;
+    for (int ka = 0; ka <= 2 * pa; ++ka) {
+        const int ja = ra + ka - pa;
+        // neighbours outside the grid are skipped, and so are those on a constrained face
+        if (ja < 0 || ja >= na) continue;
+        if (MASK && (((g.dmask & (1 << (2 * A))) && ja == 0) || ((g.dmask & (2 << (2 * A))) && ja == na - 1))) continue;
+        for (int kb = 0; kb < wb; ++kb) {
+            const int jb = rb + kb - pb;
+            if (jb < 0 || jb >= nb) continue;
+            if (MASK && (((g.dmask & (1 << (2 * B))) && jb == 0) || ((g.dmask & (2 << (2 * B))) && jb == nb - 1))) continue;
+            s = fma(Sr[ka * wb + kb], x[xo + (int64_t)(ja - ra) * st[A] + (int64_t)(jb - rb) * st[B]], s);
+        }
+    }
+    return s;
+}
+
+template <int EPI, bool TENSOR, bool MASK, bool FACE>
 __global__ void __launch_bounds__(256)
 matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1, const AssembleAxis A2,
                const double* __restrict__ x, double* __restrict__ y, const double* __restrict__ b,
                const double* __restrict__ a_q, const double* __restrict__ c_q, const double* __restrict__ diag,
                double mass_coef, double omega, double* __restrict__ partial, double* __restrict__ partial2,
-               double beta) {
+               double beta, const MatfreeFaces F) {
     __shared__ double sX[(MF_PMAX + 1) * MF_WW];   // ring of x window planes
     __shared__ double sU[2 * MF_WW];               // B0 x, B0' x
     __shared__ double sT[3 * MF_QW];               // B1 U, B1 U', B1' U  at [q1][c2]
@@ -306,6 +335,15 @@ matfree_kernel(const MatfreeGeom g, const AssembleAxis A0, const AssembleAxis A1
                     double s = sY[(jf % (p0 + 1)) * MF_DD + tid];
                     sY[(jf % (p0 + 1)) * MF_DD + tid] = 0.0;
                     const int64_t xo = (int64_t)(jf + g.pd0) * g.s0 + (int64_t)(i1 + g.pd1) * g.s1 + (i2 + g.pd2);
+                    // face terms, in the order axis 0 lo, axis 0 hi, axis 1 lo, ...
+                    if constexpr (FACE) {
+                        if ((F.mask & 1) && jf == 0) s = face_row<0, MASK>(s, F.s[0], g, p1, p2, jf, i1, i2, x, xo);
+                        if ((F.mask & 2) && jf == g.n0 - 1) s = face_row<0, MASK>(s, F.s[1], g, p1, p2, jf, i1, i2, x, xo);
+                        if ((F.mask & 4) && i1 == 0) s = face_row<1, MASK>(s, F.s[2], g, p0, p2, jf, i1, i2, x, xo);
+                        if ((F.mask & 8) && i1 == g.n1 - 1) s = face_row<1, MASK>(s, F.s[3], g, p0, p2, jf, i1, i2, x, xo);
+                        if ((F.mask & 16) && i2 == 0) s = face_row<2, MASK>(s, F.s[4], g, p0, p1, jf, i1, i2, x, xo);
+                        if ((F.mask & 32) && i2 == g.n2 - 1) s = face_row<2, MASK>(s, F.s[5], g, p0, p1, jf, i1, i2, x, xo);
+                    }
                     // a constrained row applies its diagonal entry only
                     if (MASK && (((g.dmask & 1) && jf == 0) || ((g.dmask & 2) && jf == g.n0 - 1) ||
                                     ((g.dmask & 4) && i1 == 0) || ((g.dmask & 8) && i1 == g.n1 - 1) ||
@@ -426,13 +464,13 @@ int matfree_diag_launch(const AssembleAxis* ax, const double* a_q, const double*
 // any number of registers up to 256 keeps that, scratch does not.  False, with a
 // message, if a build reports scratch or the attributes cannot be read.
 bool matfree_tensor_builds_ok(std::string* why) {
-    const void* fns[10] = {
-        (const void*)matfree_kernel<EPI_APPLY, true, false>, (const void*)matfree_kernel<EPI_RESID, true, false>,
-        (const void*)matfree_kernel<EPI_JACOBI, true, false>, (const void*)matfree_kernel<EPI_APPLYDOT, true, false>,
-        (const void*)matfree_kernel<EPI_APPLY, true, true>, (const void*)matfree_kernel<EPI_RESID, true, true>,
-        (const void*)matfree_kernel<EPI_JACOBI, true, true>, (const void*)matfree_kernel<EPI_APPLYDOT, true, true>,
-        (const void*)matfree_kernel<EPI_CHEBY, true, false>, (const void*)matfree_kernel<EPI_CHEBY, true, true>};
-    for (int k = 0; k < 10; ++k) {
+#define POMS_MF_BUILDS(E)                                                                                   \
+    (const void*)matfree_kernel<E, true, false, false>, (const void*)matfree_kernel<E, true, true, false>,     \
+    (const void*)matfree_kernel<E, true, false, true>, (const void*)matfree_kernel<E, true, true, true>
+    const void* fns[20] = {POMS_MF_BUILDS(EPI_APPLY), POMS_MF_BUILDS(EPI_RESID), POMS_MF_BUILDS(EPI_JACOBI),
+                           POMS_MF_BUILDS(EPI_APPLYDOT), POMS_MF_BUILDS(EPI_CHEBY)};
+#undef POMS_MF_BUILDS
+    for (int k = 0; k < 20; ++k) {
         hipFuncAttributes at{};
         if (hipFuncGetAttributes(&at, fns[k]) != hipSuccess) {
             (void)hipGetLastError();
@@ -453,19 +491,26 @@ bool matfree_tensor_builds_ok(std::string* why) {
 int matfree_launch(int epi, const MatfreeGeom& g, const AssembleAxis* ax, const double* x, double* y, const double* b,
                    const double* a_q, const double* c_q, const double* diag, double mass_coef, double omega,
                    double* partial, double* partial2, int max_blocks, hipStream_t st, int* nblk_out, bool tensor,
-                   double beta) {
+                   double beta, const MatfreeFaces* faces) {
     const int nb = (int)std::min<int64_t>(g.ntiles, max_blocks);
     *nblk_out = nb;
     if (nb <= 0) return 0;
-#define POMS_MF_LAUNCH1(E, T, M)                                                                              \
-    hipLaunchKernelGGL((matfree_kernel<E, T, M>), dim3(nb), dim3(256), 0, st, g, ax[0], ax[1], ax[2], x, y, b, a_q,  \
-                       c_q, diag, mass_coef, omega, partial, partial2, beta)
+    const bool face = faces && faces->mask;
+    const MatfreeFaces F = face ? *faces : MatfreeFaces{};
+#define POMS_MF_LAUNCH1(E, T, M, FC)                                                                          \
+    hipLaunchKernelGGL((matfree_kernel<E, T, M, FC>), dim3(nb), dim3(256), 0, st, g, ax[0], ax[1], ax[2], x, y, b,  \
+                       a_q, c_q, diag, mass_coef, omega, partial, partial2, beta, F)
+#define POMS_MF_LAUNCH2(E, T, M)                                                                              \
+    do {                                                                                                      \
+        if (face) POMS_MF_LAUNCH1(E, T, M, true);                                                             \
+        else POMS_MF_LAUNCH1(E, T, M, false);                                                                 \
+    } while (0)
 #define POMS_MF_LAUNCH(E)                                                                                     \
     do {                                                                                                      \
-        if (tensor && g.dmask) POMS_MF_LAUNCH1(E, true, true);                                                \
-        else if (tensor) POMS_MF_LAUNCH1(E, true, false);                                                     \
-        else if (g.dmask) POMS_MF_LAUNCH1(E, false, true);                                                    \
-        else POMS_MF_LAUNCH1(E, false, false);                                                                \
+        if (tensor && g.dmask) POMS_MF_LAUNCH2(E, true, true);                                                \
+        else if (tensor) POMS_MF_LAUNCH2(E, true, false);                                                     \
+        else if (g.dmask) POMS_MF_LAUNCH2(E, false, true);                                                    \
+        else POMS_MF_LAUNCH2(E, false, false);                                                                \
     } while (0)
     switch (epi) {
         case EPI_APPLY: POMS_MF_LAUNCH(EPI_APPLY); break;
@@ -478,6 +523,7 @@ int matfree_launch(int epi, const MatfreeGeom& g, const AssembleAxis* ax, const 
             return 1;
     }
 #undef POMS_MF_LAUNCH
+#undef POMS_MF_LAUNCH2
 #undef POMS_MF_LAUNCH1
     return 0;
 }

@@ -247,6 +247,53 @@ int stencil_to_spl_launch(const StencilGeom& g, const double* coef, double* out,
     return 0;
 }
 
+// A face term (poms_op_add_face_term) added into stored coefficients: the face stencil
+// [m_a][m_b][w_a][w_b] over the two axes of the face in increasing order goes to the rows of
+// the boundary plane `side` of axis AX at the offsets (k_a, centre on AX, k_b).  One thread
+// per (row, offset); every target entry has one owner, so there are no atomics.  diag not
+// null: the centres only, into a dense diagonal (the matrix-free form's).
+template <int AX>
+__global__ void __launch_bounds__(256)
+face_add_kernel(const StencilGeom g, int side, const double* __restrict__ face, double* __restrict__ coef,
+                double* __restrict__ diag) {
+    constexpr int A = AX == 0 ? 1 : 0, B = AX == 2 ? 1 : 2;
+    const int n[3] = {g.n0, g.n1, g.n2}, p[3] = {g.p0, g.p1, g.p2}, w[3] = {g.w0, g.w1, g.w2};
+    const int64_t total = (int64_t)n[A] * n[B] * w[A] * w[B];
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (tid >= total) return;
+    const int kb = (int)(tid % w[B]), ka = (int)((tid / w[B]) % w[A]);
+    const int64_t row = tid / ((int64_t)w[A] * w[B]);
+    int i[3], k[3];
+    i[AX] = side ? n[AX] - 1 : 0;
+    i[A] = (int)(row / n[B]);
+    i[B] = (int)(row % n[B]);
+    k[AX] = p[AX];
+    k[A] = ka;
+    k[B] = kb;
+    const int64_t lin = ((int64_t)i[0] * g.n1 + i[1]) * g.n2 + i[2];
+    if (diag) {
+        if (ka == p[A] && kb == p[B]) diag[lin] += face[tid];
+        return;
+    }
+    coef[(int64_t)((k[0] * g.w1 + k[1]) * g.w2 + k[2]) * g.cstride + lin] += face[tid];
+}
+
+int face_add_launch(const StencilGeom& g, int axis, int side, const double* face, double* coef, double* diag,
+                    hipStream_t st) {
+    const int n[3] = {g.n0, g.n1, g.n2}, w[3] = {g.w0, g.w1, g.w2};
+    const int a = axis == 0 ? 1 : 0, b = axis == 2 ? 1 : 2;
+    const int64_t total = (int64_t)n[a] * n[b] * w[a] * w[b];
+    if (total == 0) return 0;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (axis == 0)
+        hipLaunchKernelGGL(face_add_kernel<0>, grid, dim3(256), 0, st, g, side, face, coef, diag);
+    else if (axis == 1)
+        hipLaunchKernelGGL(face_add_kernel<1>, grid, dim3(256), 0, st, g, side, face, coef, diag);
+    else
+        hipLaunchKernelGGL(face_add_kernel<2>, grid, dim3(256), 0, st, g, side, face, coef, diag);
+    return 0;
+}
+
 // Blocks of the grid-stride launch (<= max_blocks so the partials fit the scratch).
 int stencil_launch(int epi, const StencilGeom& g, const double* coef, const double* x, double* y,
                    const double* b, double omega, double* partial, double* partial2, int max_blocks,

@@ -75,6 +75,26 @@ def pullback(J, a=None, c=None, mass_coef: float = 1.0):
     return G, gamma, det.contiguous()
 
 
+def surface_measure(J, axis: int):
+    """The surface Jacobian of the face ``ξ_axis = const`` from the Jacobian ``J[i][k] =
+    ∂F_i/∂ξ_k`` at a grid of points on it (the nested tensors :meth:`_MappingBase.jacobian`
+    returns for a grid whose ``axis`` has one point): ``|∂F/∂ξ_t|`` in 2D (``t`` the other
+    axis), ``|∂F/∂ξ_a × ∂F/∂ξ_b|`` in 3D (``a``, ``b`` the other two).  Closed form,
+    elementwise torch operations on the Jacobian's device; the result has the grid's shape."""
+    d = _grid(J)
+    if not 0 <= int(axis) < d:
+        raise ValueError(f"axis must be 0 .. {d - 1}, got {axis}")
+    J = [[torch.as_tensor(J[i][k], dtype=F64) for k in range(d)] for i in range(d)]
+    if d == 2:
+        t = 1 - int(axis)
+        return torch.sqrt(J[0][t] * J[0][t] + J[1][t] * J[1][t])
+    a, b = [k for k in range(3) if k != int(axis)]
+    n0 = J[1][a] * J[2][b] - J[2][a] * J[1][b]
+    n1 = J[2][a] * J[0][b] - J[0][a] * J[2][b]
+    n2 = J[0][a] * J[1][b] - J[1][a] * J[0][b]
+    return torch.sqrt(n0 * n0 + n1 * n1 + n2 * n2)
+
+
 class _MappingBase:
     """``physical`` and ``jacobian`` at a tensor grid of points; :meth:`pullback` on top."""
 
@@ -206,16 +226,35 @@ class MappedDomain:
         """``(G, gamma, det)`` at the quadrature points."""
         return self.mapping.pullback(self.points, a=a, c=c, mass_coef=mass_coef, device=self._dev)
 
-    def operator(self, a=None, c=None, mass_coef: float = 1.0, matrix_free: bool = False, dirichlet=None):
+    def operator(self, a=None, c=None, mass_coef: float = 1.0, matrix_free: bool = False, dirichlet=None,
+                 robin=None):
         """``-∇·(a∇u) + c u`` on the physical domain, as the stored stencil or
         (``matrix_free``) a :class:`~poms_amd.matfree.MatrixFreeOperator`; ``dirichlet``:
-        its constrained faces (:mod:`poms_amd.boundary`)."""
+        its constrained faces; ``robin``: ``{(axis, side): β}`` (or a ``RobinBC``), the Robin faces
+        ``a ∂ₙu + β u = g`` of the physical boundary, β a scalar or a function of the physical
+        coordinates (:mod:`poms_amd.boundary`)."""
         G, gamma, _ = self.pullback(a, c, mass_coef)
+        rb = self.robin(robin) if robin is not None else None
         if matrix_free:
             from .matfree import MatrixFreeOperator
-            return MatrixFreeOperator(self.space, self.knots, a=G, c=gamma, nquad=self.nquad, dirichlet=dirichlet)
+            return MatrixFreeOperator(self.space, self.knots, a=G, c=gamma, nquad=self.nquad, dirichlet=dirichlet,
+                                      robin=rb)
         from .assembly import assemble_stencil
-        return assemble_stencil(self.space, self.knots, a=G, c=gamma, nquad=self.nquad, dirichlet=dirichlet)
+        return assemble_stencil(self.space, self.knots, a=G, c=gamma, nquad=self.nquad, dirichlet=dirichlet, robin=rb)
+
+    def robin(self, robin):
+        """The :class:`~poms_amd.boundary.RobinBC` of the domain: β and the face data as
+        functions of the physical coordinates, the face integrals with the surface measure.
+        A ``RobinBC`` is returned as it is."""
+        from .boundary import RobinBC
+        if isinstance(robin, RobinBC):
+            return robin
+        return RobinBC(self.space, self.knots, robin, mapping=self.mapping, nquad=self.nquad)
+
+    def boundary_load(self, g, out=None):
+        """``∫_Γ g φ_i ds`` over the faces of ``g = {(axis, side): data}`` on the physical
+        boundary, added into ``out`` (default: a zero vector)."""
+        return self.robin(None).load_vector(g, out)
 
     def dirichlet(self, faces):
         """The :class:`~poms_amd.boundary.DirichletBC` of the domain: boundary data as a

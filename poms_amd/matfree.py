@@ -23,6 +23,7 @@ import torch
 from . import _lib
 from .assembly import (_coef_field, assemble_stencil, axis_tables, quadrature_args, split_coef, tensor_coef,
                        tensor_ncomp, used_in_place)
+from .boundary import add_face_term
 from .mg import GalerkinVCycle, uniform_hierarchy
 from .stencil import KronOperator, StencilVectorSpace
 
@@ -78,10 +79,12 @@ class MatrixFreeOperator(KronOperator):
     operator unchanged.  :meth:`assemble` gives the stored stencil of the same
     arguments for cross-checks.  ``dirichlet`` / :meth:`set_dirichlet`: constrained faces
     (:mod:`poms_amd.boundary`); the stored diagonal stays that of the unconstrained
-    operator."""
+    operator.  ``robin``: ``{(axis, side): β}`` or a :class:`~poms_amd.boundary.RobinBC` of the
+    space: the face masses ``S`` are kept beside the quadrature form and applied by the
+    kernel's ``FACE`` builds, and the stored diagonal is that of ``A + S``."""
 
     def __init__(self, V: StencilVectorSpace, knots, a=None, c=None, mass_coef: float = 1.0,
-                 nquad: int | None = None, dirichlet=None):
+                 nquad: int | None = None, dirichlet=None, robin=None):
         if V.is_cart or V.is_distributed or tuple(V.local_npts) != tuple(V.npts):
             raise NotImplementedError("matrix-free operators are implemented for undistributed spaces "
                                       "(no slab or Cart decomposition)")
@@ -109,6 +112,9 @@ class MatrixFreeOperator(KronOperator):
                           None if self._aq is None else C.c_void_p(self._aq.data_ptr()), *tail)
         except _lib.PomsError as e:
             raise ValueError(str(e)) from None
+        if robin is not None:
+            from .boundary import RobinBC
+            (robin if isinstance(robin, RobinBC) else RobinBC(V, self.knots, robin, nquad=nquad)).apply(self)
         if dirichlet is not None:
             self.set_dirichlet(dirichlet)
 
@@ -136,8 +142,13 @@ class MatrixFreeOperator(KronOperator):
         a, c = self._args
         to_np = lambda f: f.cpu().numpy() if isinstance(f, torch.Tensor) else f
         # (a tensor coefficient goes on as the device array the operator holds)
-        return assemble_stencil(self.space, self.knots, a=self._aq if self.tensor else to_np(a), c=to_np(c),
-                                mass_coef=self.mass_coef, nquad=self.nquad, dirichlet=self.dirichlet)
+        B = assemble_stencil(self.space, self.knots, a=self._aq if self.tensor else to_np(a), c=to_np(c),
+                             mass_coef=self.mass_coef, nquad=self.nquad)
+        for face, S in self._face_terms:   # (the same face terms, before the mask)
+            add_face_term(B, face, S)
+        if self.dirichlet is not None:
+            B.set_dirichlet(self.dirichlet)
+        return B
 
     def _no_matrix(self, what):
         raise NotImplementedError(f"a matrix-free operator stores no coefficients: {what} is not available; "
@@ -187,13 +198,17 @@ class MatrixFreeVCycle(GalerkinVCycle):
     @classmethod
     def uniform(cls, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *, a=None, c=None,
                 mass_coef: float = 1.0, nquad: int | None = None, device=None, tol: float = 1e-6, maxiters=None,
-                mapping=None, dirichlet=None, **smoother_kw):
+                mapping=None, dirichlet=None, robin=None, **smoother_kw):
         """Dyadic uniform hierarchy, as :meth:`GalerkinVCycle.uniform`.  ``a`` / ``c``:
         None, scalars or callables (they are sampled on two quadrature grids, the
         finest level's and level 1's).  ``mapping``: the operator of the mapped domain
         (:mod:`poms_amd.geometry`), its tensor sampled on those two grids; ``a`` / ``c``
-        are then functions of the physical coordinates.  ``smoother_kw``: ``smoother``,
-        ``cheby_degree``, ``cheby_ratio``, ``cheby_safety`` of :class:`~poms_amd.mg.GalerkinVCycle`."""
+        are then functions of the physical coordinates.  ``robin``: ``{(axis, side): β}``, β a
+        scalar or a callable (:class:`~poms_amd.boundary.RobinBC`), sampled on both levels too:
+        level 1 is rediscretised with the same ``robin`` on its own knots.  ``smoother_kw``:
+        ``smoother``, ``cheby_degree``, ``cheby_ratio``, ``cheby_safety`` of
+        :class:`~poms_amd.mg.GalerkinVCycle`."""
+        from .boundary import RobinBC
         for f in (a, c):
             if f is not None and not callable(f) and np.ndim(f) != 0:
                 raise ValueError("a / c must be None, scalars or callables here: they are sampled on two grids")
@@ -203,9 +218,14 @@ class MatrixFreeVCycle(GalerkinVCycle):
             pull = lambda T: mapping.pullback([axis_tables(T, p, nquad)["points"].reshape(-1)] * ndim, a=a, c=c,
                                               mass_coef=mass_coef, device=f"cuda:{V.device}")[:2]
             (a, c), (a1, c1) = pull(knots[0]), pull(knots[1])
-        A = MatrixFreeOperator(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef, nquad=nquad, dirichlet=dirichlet)
         V1 = StencilVectorSpace([len(knots[1]) - p - 1] * ndim, [p] * ndim, device=V.device, align=True)
-        A1 = assemble_stencil(V1, [knots[1]] * ndim, a=a1, c=c1, mass_coef=mass_coef, nquad=nquad)
+        r0 = r1 = None
+        if robin:
+            r0 = RobinBC(V, [knots[0]] * ndim, robin, mapping=mapping, nquad=nquad)
+            r1 = RobinBC(V1, [knots[1]] * ndim, robin, mapping=mapping, nquad=nquad)
+        A = MatrixFreeOperator(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef, nquad=nquad, dirichlet=dirichlet,
+                               robin=r0)
+        A1 = assemble_stencil(V1, [knots[1]] * ndim, a=a1, c=c1, mass_coef=mass_coef, nquad=nquad, robin=r1)
         mg = cls(A, [[P1l] * ndim for P1l in P1], A1, tol=tol, maxiters=maxiters, **smoother_kw)
         mg.p, mg.ndim, mg.cells, mg.knots, mg.P1 = int(p), int(ndim), cells, knots, P1
         return mg

@@ -432,21 +432,26 @@ class GalerkinVCycle(_VCycle):
     @classmethod
     def uniform(cls, p: int, ncells_fine: int, ncells_coarsest: int = 8, ndim: int = 3, *, a=None, c=None,
                 mass_coef: float = 1.0, device=None, tol: float = 1e-6, maxiters=None, mapping=None,
-                dirichlet=None, **smoother_kw):
+                dirichlet=None, robin=None, **smoother_kw):
         """Dyadic uniform hierarchy (as :class:`MultilevelVCycle`'s) under
         ``-∇·(a∇u) + c u`` assembled on the finest knots by
         :func:`~poms_amd.assembly.assemble_stencil`.  ``mapping`` (a
         :class:`~poms_amd.geometry.Mapping` or ``SplineMapping``): the operator of the
         mapped domain, its tensor sampled on the finest quadrature grid (``a`` / ``c``
-        are then functions of the physical coordinates).  ``smoother_kw``: ``smoother``,
-        ``cheby_degree``, ``cheby_ratio``, ``cheby_safety`` of the constructor."""
+        are then functions of the physical coordinates).  ``robin``: ``{(axis, side): β}``, β a
+        scalar or a callable (:class:`~poms_amd.boundary.RobinBC`), sampled on the finest level
+        only: the coarse operators are Galerkin products of the stored ``A + S``.
+        ``smoother_kw``: ``smoother``, ``cheby_degree``, ``cheby_ratio``, ``cheby_safety`` of the
+        constructor."""
         from .assembly import assemble_stencil, axis_tables
+        from .boundary import RobinBC
         _check_smoother(smoother_kw.get("smoother", "jacobi"))
         cells, knots, P1, V = uniform_hierarchy(p, ncells_fine, ncells_coarsest, ndim, device)
         if mapping is not None:
             pts = axis_tables(knots[0], p)["points"].reshape(-1)
             a, c, _ = mapping.pullback([pts] * ndim, a=a, c=c, mass_coef=mass_coef, device=f"cuda:{V.device}")
-        A = assemble_stencil(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef, dirichlet=dirichlet)
+        rb = RobinBC(V, [knots[0]] * ndim, robin, mapping=mapping) if robin else None
+        A = assemble_stencil(V, [knots[0]] * ndim, a=a, c=c, mass_coef=mass_coef, dirichlet=dirichlet, robin=rb)
         mg = cls(A, [[P1l] * ndim for P1l in P1], tol=tol, maxiters=maxiters, **smoother_kw)
         mg.p, mg.ndim, mg.cells, mg.knots, mg.P1 = int(p), int(ndim), cells, knots, P1
         return mg

@@ -245,6 +245,19 @@ def constrain_1d(band: np.ndarray, lo: bool, hi: bool) -> np.ndarray:
     return band
 
 
+def robin_1d(K_band: np.ndarray, beta_lo: float = 0.0, beta_hi: float = 0.0) -> np.ndarray:
+    """``K + β_lo e₀e₀ᵀ + β_hi eₙ₋₁eₙ₋₁ᵀ`` in band form: a constant Robin coefficient on the
+    end points of an axis of a Kronecker operator (:mod:`poms_amd.boundary`).  On open knots
+    only the end function is non-zero at an end point, where it equals 1, so the 0-dimensional
+    face mass is ``β`` on the corner entry; ``(K + β e eᵀ)⊗M⊗M = K⊗M⊗M + β e eᵀ⊗M⊗M`` then
+    carries the face mass ``β M⊗M`` of the higher-dimensional face."""
+    band = np.array(K_band, dtype=np.float64, order="C")
+    p = (band.shape[1] - 1) // 2
+    band[0, p] += float(beta_lo)
+    band[-1, p] += float(beta_hi)
+    return band
+
+
 def insert_knot_matrix(T: np.ndarray, p: int, t: float):
     """Boehm single-knot insertion: returns ``(A, T_new)`` with ``A`` of shape ``(n+1, n)``.
 

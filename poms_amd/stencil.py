@@ -544,6 +544,8 @@ class KronOperator:
         self.pads, self.starts, self.ends = V.pads, V.starts, V.ends
         self._dirichlet = None   # constrained faces ((lo, hi) per axis), see poms_amd.boundary
         self._lmax_est = None    # solvers.estimate_lmax's value (dropped when the operator changes)
+        self._face_terms = []    # general forms: ((axis, side), stencil) of every face term the handle carries (boundary.add_face_term)
+        self.robin = None        # Kronecker forms: the constant Robin coefficients in the factors (laplace(robin=))
 
     # -- Dirichlet faces ---------------------------------------------------------
     @property
@@ -570,6 +572,17 @@ class KronOperator:
         if f != self._dirichlet:
             self._lmax_est = None
         self._dirichlet = f
+
+    def face_terms(self):
+        """The faces ``(axis, side)`` of a general form that carry a Robin term
+        (``poms_op_face_terms``; :class:`poms_amd.boundary.RobinBC`).  A stored stencil that is
+        edited on the host afterwards is uploaded again as plain coefficients: they keep the
+        terms, the new handle names no face and the operator's list of terms is emptied with it."""
+        if self.form not in ("stencil", "matfree"):
+            return tuple(self.robin or ())
+        m = C.c_int(0)
+        _lib.call("poms_op_face_terms", self._h, C.byref(m))
+        return tuple((b // 2, b % 2) for b in range(2 * self.space.ndim) if m.value >> b & 1)
 
     def _push_dirichlet(self, h, faces) -> None:
         from .boundary import faces_mask
@@ -629,19 +642,32 @@ class KronOperator:
 
     # -- constructors ------------------------------------------------------------
     @classmethod
-    def laplace(cls, V: StencilVectorSpace, M: Sequence, K: Sequence, mass_coef: float = 1.0, dirichlet=None):
+    def laplace(cls, V: StencilVectorSpace, M: Sequence, K: Sequence, mass_coef: float = 1.0, dirichlet=None,
+                robin=None):
         """-Δu + c u in Kronecker-sum form from per-axis 1D (mass, stiffness) bands.
         ``dirichlet``: constrained faces (:func:`poms_amd.boundary.normalize_faces`); the
         factors of a constrained axis go through :func:`~poms_amd.splines.constrain_1d`,
         so the free rows are those of ``Π A Π`` and the constrained rows decouple from
-        them (into an SPD block that is not diagonal)."""
-        from .boundary import normalize_faces
-        from .splines import constrain_1d
+        them (into an SPD block that is not diagonal).  ``robin``: ``{(axis, side): β}`` with
+        constant ``β`` (no mapping), the face mass of ``∂ₙu + β u = g`` added through the
+        stiffness factor of the face's axis (:func:`~poms_amd.splines.robin_1d`, before the
+        Dirichlet faces are constrained); a callable ``β`` raises ``ValueError``: it needs a
+        general form (:class:`~poms_amd.boundary.RobinBC`)."""
+        from .boundary import normalize_faces, normalize_robin
+        from .splines import constrain_1d, robin_1d
         nd = V.ndim
         M = [_band_of(m) for m in M]
         K = [_band_of(k) for k in K]
         if len(M) != nd or len(K) != nd:
             raise ValueError("need one (M, K) pair per axis")
+        rb = normalize_robin(robin, nd)
+        if rb:
+            if any(callable(beta) or np.ndim(beta) != 0 for beta in rb.values()):
+                raise ValueError("robin: a Kronecker operator takes constant β only (a variable β is not a Kronecker "
+                                 "sum: use assemble_stencil or MatrixFreeOperator)")
+            if V.is_distributed or V.is_cart:
+                raise NotImplementedError("robin: distributed (slab / Cart) spaces are not supported")
+            K = [robin_1d(k, rb.get((d, 0), 0.0), rb.get((d, 1), 0.0)) for d, k in enumerate(K)]
         faces = normalize_faces(dirichlet, nd)
         if faces is not None:
             if V.is_distributed or V.is_cart:
@@ -664,6 +690,7 @@ class KronOperator:
         op = cls(V, "sum", bands, pmax)
         op.M, op.K, op.mass_coef = M, K, c
         op._dirichlet = faces
+        op.robin = rb or None
         return op
 
     @classmethod
@@ -1250,6 +1277,7 @@ class StencilMatrix(KronOperator):
         self._hh = h
         self._dirty = False
         self._lmax_est = None
+        self._face_terms = []   # (the uploaded coefficients hold the terms; the new handle names no face)
         if self._dirichlet is not None:   # (a new handle starts unconstrained)
             self._push_dirichlet(h, self._dirichlet)
 
