@@ -33,12 +33,13 @@
 extern "C" {
 #endif
 
-#define POMS_ABI_VERSION 11 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
+#define POMS_ABI_VERSION 12 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
                              * 7: poms_pcg_opts.n_pbuf, .pbuf;
                              * 8: poms_op_set_dirichlet, poms_op_get_dirichlet;
                              * 9: poms_op_cheby_step, poms_op_cheby_supported;
                              * 10: poms_op_papply_dot (+ _supported, _count), poms_pcg_p_update_dev;
-                             * 11: poms_op_add_face_term, poms_op_face_terms */
+                             * 11: poms_op_add_face_term, poms_op_face_terms;
+                             * 12: poms_op_rjacobi0 (+ _supported, _count), poms_pcg_opts.fold_r */
 
 /* operator forms (see poms_op_create) */
 #define POMS_FORM_SINGLE 0 /* y = F0 (x) F1 (x) F2 x                                  */
@@ -307,6 +308,26 @@ int poms_op_papply_dot_supported(poms_op* op, const double* s, const double* p, 
 int poms_op_papply_dot(poms_op* op, const double* beta_dev, const double* s, const double* p,
                        double* p_next, double* q, double* dot_out, void* stream);
 int poms_op_papply_dot_count(poms_op* op, int64_t* count);
+/* pcg's r update formed inside the first launch of the preconditioner call that follows it,
+ * over every plane: r_new = r - alpha_dev[0] q (the fma of poms_pcg_r_update_dev) and the two
+ * damped-Jacobi sweeps from x = 0 on r_new into x_out, with the bits of poms_pcg_r_update_dev
+ * followed by poms_op_jacobi_from_zero; r_new is never read back, and must be another vector
+ * than r (the launch reads r's halo rows while other workgroups store r_new).  Only r_new's
+ * interior points are stored: its ghost cells must be zero already.  The four vectors must be
+ * distinct.  sums_out (device, or NULL: no sums): [||dr_2||^2, ||x1||^2] as the two sweeps
+ * from zero give them, and r_new . r_new added in the order of the launch's tiles -- not the
+ * bits of poms_pcg_r_update_dev's sum, which differ from it by at most a few n 2^-53 of
+ * its value (n: the vector's length).
+ * Where it runs (poms_op_rjacobi0_supported): one rank, 3D Kronecker-sum operators at p = 3
+ * on kernel variant 8 or 10 whose axes 1 and 2 share their interior rows, r, q and r_new on
+ * the same side of the line alignment (poms_layout.pitch).  poms_op_rjacobi0_count: such
+ * launches so far, the native pcg loop's included, and (exact, or NULL) the exact r.r passes
+ * that loop queued behind them (POMS_PCG_RFOLD=0 keeps that loop on the two launches).      */
+int poms_op_rjacobi0_supported(poms_op* op, const double* r, const double* q, const double* r_new,
+                               const double* x_out, int* yes);
+int poms_op_rjacobi0(poms_op* op, double omega, const double* alpha_dev, const double* r, const double* q,
+                     double* r_new, double* x_out, double* sums_out, void* stream);
+int poms_op_rjacobi0_count(poms_op* op, int64_t* count, int64_t* exact);
 /* r = b - A x (fused).  Replaces: `r = b - A.dot(x)` at `sources/solvers.py:85`,
  * `sources/solvers.py:209`, `sources/mg_jac.py:93`.                           */
 int poms_op_residual(poms_op* op, const double* b, const double* x, double* r,
@@ -665,6 +686,13 @@ typedef struct poms_pcg_opts {
                       * not in speculative mode; else, and with 0, x is updated every
                       * iteration.  At most 15 are used.                                  */
     double* const* pbuf;
+    int fold_r;      /* (ABI 12) non-zero, with skip_tail and deferred x updates: where
+                      * poms_op_rjacobi0 runs, an iteration's r update is formed inside its
+                      * preconditioner call's first launch, and the stop test r.r < tol ||r0||
+                      * is decided from that launch's sum where it lies outside a guard band
+                      * of a few n 2^-53 around the threshold, else from the r update's own
+                      * sum, formed from the stored r: the same x and info.  One more vector
+                      * of memory, kept by the operator.                                   */
 } poms_pcg_opts;
 typedef struct poms_pcg_info {
     int niter;

@@ -43,7 +43,8 @@ class Layout(C.Structure):
 class PcgOpts(C.Structure):
     _fields_ = [("tol", C.c_double), ("maxiter", C.c_int), ("jtol", C.c_double), ("jmaxiter", C.c_int),
                 ("omega", C.c_double), ("prev", C.c_int), ("next", C.c_int), ("skip_tail", C.c_int),
-                ("n_pbuf", C.c_int), ("pbuf", C.POINTER(C.c_void_p))]   # (ABI 7; default 0 / NULL)
+                ("n_pbuf", C.c_int), ("pbuf", C.POINTER(C.c_void_p)),   # (ABI 7; default 0 / NULL)
+                ("fold_r", C.c_int)]                                    # (ABI 12; default 0)
 
 
 class PcgInfo(C.Structure):
@@ -127,6 +128,9 @@ _SIGS = {
     "poms_op_papply_dot_supported": [_vp, _vp, _vp, _vp, _vp, C.POINTER(_i)],
     "poms_op_papply_dot": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "poms_op_papply_dot_count": [_vp, C.POINTER(_i64)],
+    "poms_op_rjacobi0_supported": [_vp, _vp, _vp, _vp, _vp, C.POINTER(_i)],
+    "poms_op_rjacobi0": [_vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "poms_op_rjacobi0_count": [_vp, C.POINTER(_i64), C.POINTER(_i64)],
     "poms_pcg_p_update_dev": [_vp, _LP, _vp, _vp, _vp, _vp, _vp],
     "poms_op_jacobi_sweep": [_vp, _d, _vp, _vp, _vp, _i64, _i64, _i, _vp],
     "poms_op_jacobi_sweep_dot": [_vp, _d, _vp, _vp, _vp, _i64, _i64, _i, _vp],

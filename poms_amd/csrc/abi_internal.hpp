@@ -108,10 +108,16 @@ struct poms_op {
     // pcg_native.hip's diag_scale_norm writes it too)
     int64_t last_partials = 0;
     int64_t papply_launches = 0;   // EPI_PAPPLYDOT launches so far (poms_op_papply_dot_count)
+    int64_t rfold_launches = 0;    // EPI_RJACOBI0 launches so far (poms_op_rjacobi0_count)
+    int64_t rfold_exact = 0;       // exact r.r passes the native pcg loop queued behind them (V_SQNORM)
 
     // ---- native pcg loop (pcg_native.hip only; freed by poms_op_destroy) ----
     double* sv_dev = nullptr;        // device scalars, then the deferred x pass's alphas
     poms::PcgSlots* sv = nullptr;    // the pinned host-sum slots (pcg_slots_free)
+    // the folded r update's second r buffer (zero ghosts), placed as la_buf is: rf_buf sits
+    // rf_off doubles into rf_raw, on the work vectors' 128-B phase
+    double *rf_buf = nullptr, *rf_raw = nullptr, *rf_part = nullptr;   // (rf_part: kScratch partials behind it)
+    int64_t rf_off = -1, rf_n = 0;
     double* la_buf = nullptr;   // the two-sweep lookahead's fourth preconditioner buffer (zero ghosts)
     double* la_raw = nullptr;   // its allocation: la_buf sits la_off doubles in, on the work vectors' 128-B phase
     int64_t la_off = -1;
@@ -261,6 +267,9 @@ bool sweep2_ok(const poms_op* o);
 // EPI_PAPPLYDOT can run y2 = b + beta x, y = A y2 on these vectors with the bits of the flat
 // p update followed by EPI_APPLYDOT on y2 (papply_ok's comment in abi_op.hip)
 bool papply_ok(const poms_op* o, const double* x, const double* b, const double* y2, const double* y);
+// EPI_RJACOBI0 can run y2 = x - alpha b and the two sweeps from zero on y2 with the bits of the
+// flat r update followed by EPI_JACOBI0 (rfold_ok's comment in abi_op.hip)
+bool rfold_ok(const poms_op* o, const double* x, const double* b, const double* y2, const double* y);
 int op_run_epi(poms_op* op, const OpLaunch& q);
 int op_run_split(poms_op* op, const OpLaunch& interior, int64_t b1s, int64_t b1e, int64_t b2s, int64_t b2e,
                  double* norm_out, double* dot_out, const SplitHooks& h);

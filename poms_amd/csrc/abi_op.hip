@@ -300,6 +300,20 @@ bool poms::papply_ok(const poms_op* o, const double* x, const double* b, const d
     return v5_aligned(o, x) == v5_aligned(o, y2);
 }
 
+// EPI_RJACOBI0 (kron_v5_kernel.hpp): y2 = x - alpha b formed inside the two sweeps from zero
+// on y2.  It runs where those sweeps run the 16-wave v5 build (3D FORM_SUM, p = 3, axes 1 and
+// 2 sharing their Toeplitz rows; not the diagnostic builds) on one rank without ghost data
+// (the launch stores y2's interior points only: its pads must be zero already), and where the
+// launch takes the tile geometry of the sweeps on y2 it replaces, so that their sums keep
+// their bits: x, b and y2 on the same side of v5's line alignment.
+bool poms::rfold_ok(const poms_op* o, const double* x, const double* b, const double* y2, const double* y) {
+    if (!o || !x || !b || !y2 || !y || x == b || x == y2 || x == y || b == y2 || b == y || y2 == y) return false;
+    if (general_form(o) || distributed(o) || o->ndim != 3 || o->pmax != 3 || o->variant > 10) return false;
+    if (!variant_can(o, CAP_FROM_ZERO) || resolve_variant(o, EPI_JACOBI0) != 10) return false;
+    if (!same_toeplitz12(o->tc, o->pmax) || padded_len(o) * 8 >= 0x7ffffff0LL) return false;
+    return v5_aligned(o, x) == v5_aligned(o, y2) && v5_aligned(o, x) == v5_aligned(o, b);
+}
+
 // Two Jacobi sweeps per launch (EPI_JACOBI2, kron_2d.hip): one-rank 2D p = 3
 // Kronecker operators whose single sweep runs the v3 whole-array kernel (variant 9),
 // whose bits the two-sweep kernel reproduces
@@ -315,15 +329,18 @@ bool poms::sweep2_ok(const poms_op* o) {
 // part_off.  The scratch must hold them even when the route takes them.  `three`
 // (EPI_JACOBI3Z): three sums side by side from *pn, which the scratch holds only in its
 // default layout and need not hold when the route takes them.
+// `extra` (EPI_RJACOBI0: 1): further sums of nblk partials behind the dots, in the scratch's
+// default layout only.
 static int part_place(poms_op* o, int64_t nblk, bool wn, bool wd, bool three, PartRoute* route, double** pn,
-                      double** pd) {
+                      double** pd, int extra = 0) {
     if (route) route->used = false;
     *pn = *pd = nullptr;
     if (!wn && !wd) return 0;
     const int64_t dbase = o->dot_base < 0 ? nblk : o->dot_base;
     const bool fits = three ? o->part_off == 0 && o->dot_base < 0 && 3 * nblk <= kScratch
+                    : extra ? o->part_off == 0 && o->dot_base < 0 && (2 + extra) * nblk <= kScratch
                             : o->part_off + nblk <= dbase && dbase + o->part_off + nblk <= kScratch;
-    const bool sink = route && route->dst && (three ? 3 : (wn ? 1 : 0) + (wd ? 1 : 0)) * nblk <= route->cap;
+    const bool sink = route && route->dst && (three ? 3 : (wn ? 1 : 0) + (wd ? 1 : 0) + extra) * nblk <= route->cap;
     if (!fits && !(three && sink)) { set_error("too many blocks for the partial-sum scratch"); return 1; }
     *pn = sink ? route->dst : o->ctx->scratch + o->part_off;
     *pd = sink ? route->dst + (wn ? nblk : 0) : o->ctx->scratch + dbase + o->part_off;
@@ -417,6 +434,10 @@ static int op_run(poms_op* o, const OpLaunch& q) {
         set_error("p update + apply + x.y: v5's 16-wave tiles on one rank, five distinct arguments (poms_op_papply_dot_supported)");
         return 1;
     }
+    if (epi == EPI_RJACOBI0 && (!q.beta_dev || !rfold_ok(o, q.x, q.b, q.y2, q.y))) {
+        set_error("r update + two sweeps from zero: v5's p = 3 16-wave tiles on one rank, four distinct arguments (poms_op_rjacobi0_supported)");
+        return 1;
+    }
     if (epi == EPI_JACOBI2 || epi == EPI_JACOBI3Z) return op_run_j2(o, q);
     if (o->form == FORM_STENCIL) return stencil_run(o, q);
     if (o->form == FORM_MATFREE) return matfree_run(o, q);
@@ -425,7 +446,8 @@ static int op_run(poms_op* o, const OpLaunch& q) {
         set_error("apply + x.y: kernel variants 4, 8, 9, 10 only");
         return 1;
     }
-    if (want_dot && ((epi != EPI_JACOBI && epi != EPI_JACOBI0 && epi != EPI_APPLYDOT && epi != EPI_PAPPLYDOT) ||
+    if (want_dot && ((epi != EPI_JACOBI && epi != EPI_JACOBI0 && epi != EPI_APPLYDOT && epi != EPI_PAPPLYDOT &&
+                      epi != EPI_RJACOBI0) ||
                      !fused_dot_ok(o))) {
         set_error("fused x_out.b needs a Jacobi sweep on kernel variants 4-10");
         return 1;
@@ -441,18 +463,24 @@ static int op_run(poms_op* o, const OpLaunch& q) {
     // v4 for apply / residual at p <= 3.  Fused dots and two-sweeps-from-zero: 9.
     // Variant 10 (v5) runs apply / residual / Jacobi / apply+dot of 3D p <= 3
     // operators, and is what 8 picks for them; 9 otherwise.
-    int v = resolve_variant(o, epi);
+    // (EPI_RJACOBI0: the variant, tiles and chunks of the two sweeps from zero it contains)
+    const int gepi = epi == EPI_RJACOBI0 ? (int)EPI_JACOBI0 : epi;
+    int v = resolve_variant(o, gepi);
     const int v5_diag = (v >= 101 && v <= 114) ? v - 100 : 0;   // v5 diagnostic / tuning builds
     if (v5_diag) v = 10;
     o->last_variant = v5_diag ? 100 + v5_diag : v;
     int v5_h = 0, v5_to = 0;
     if (v == 10) kron_v5_tile(o->pmax, v5_aligned(o, q.x), &v5_h, &v5_to);
     KronGeom g;
-    if (op_geom(o, q, g, v, v5_to)) return 1;
+    OpLaunch qg = q;
+    qg.epi = gepi;
+    if (op_geom(o, qg, g, v, v5_to)) return 1;
     const int64_t nblk = (int64_t)g.tiles2 * g.tiles1 * g.nchunks;
     if (nblk == 0) { o->last_partials = 0; return 0; }
     double *pn = nullptr, *pd = nullptr;
-    if (part_place(o, nblk, want_norm, want_dot, false, q.route, &pn, &pd)) return 1;
+    // (EPI_RJACOBI0's third sum, ||y2||^2: nblk partials behind the dots)
+    if (part_place(o, nblk, want_norm, want_dot, false, q.route, &pn, &pd, epi == EPI_RJACOBI0 && want_dot ? 1 : 0))
+        return 1;
     KronPtrs p{q.x, q.y, q.b, o->a0t, o->b0t, o->a1, o->b1, o->a2, o->b2, want_norm ? pn : nullptr,
                want_dot ? pd : nullptr, o->rdiag0, q.y2, q.beta_dev};
     poms_op::TimedLaunch* tlh = nullptr;
@@ -470,6 +498,7 @@ static int op_run(poms_op* o, const OpLaunch& q) {
     POMS_HIP_CHECK(hipGetLastError());
     o->last_partials = (want_norm || want_dot) ? nblk : 0;
     if (epi == EPI_PAPPLYDOT) ++o->papply_launches;
+    if (epi == EPI_RJACOBI0) ++o->rfold_launches;
     return 0;
 }
 
@@ -512,6 +541,11 @@ int poms::op_run_epi(poms_op* op, const OpLaunch& in) {
         case EPI_APPLYDOT:
             if (q.x == q.y) { set_error("apply: y must not alias x"); return 1; }
             if (wn || !wd) { set_error("apply + dot: dot_out only"); return 1; }
+            break;
+        case EPI_RJACOBI0:   // y2 = x - alpha b, two sweeps from zero on y2: the sums of EPI_JACOBI0, and ||y2||^2
+            // (poms_op_run_reduce cannot name y2 and alpha: not one of its epilogues)
+            if (!q.y2 || !q.beta_dev) { set_error("poms_op_run_reduce: bad epilogue"); return 1; }
+            if (wn != wd) { set_error("r update + jacobi from zero: all three sums or none"); return 1; }
             break;
         case EPI_PAPPLYDOT:   // y2 = b + beta x, y = A y2, dot_out <- y2 . y
             // (poms_op_run_reduce cannot name y2 and beta: not one of its epilogues)
@@ -892,6 +926,41 @@ int poms_op_papply_dot(poms_op* op, const double* beta_dev, const double* s, con
 int poms_op_papply_dot_count(poms_op* op, int64_t* count) {
     if (!op || !count) { set_error("poms_op_papply_dot_count: null argument"); return 1; }
     *count = op->papply_launches;
+    return 0;
+}
+
+int poms_op_rjacobi0_supported(poms_op* op, const double* r, const double* q, const double* r_new, const double* x_out,
+                               int* yes) {
+    if (!op || !yes) { set_error("poms_op_rjacobi0_supported: null argument"); return 1; }
+    *yes = rfold_ok(op, r, q, r_new, x_out) ? 1 : 0;
+    return 0;
+}
+
+int poms_op_rjacobi0(poms_op* op, double omega, const double* alpha_dev, const double* r, const double* q,
+                     double* r_new, double* x_out, double* sums_out, void* stream) {
+    if (!op || !alpha_dev || !r || !q || !r_new || !x_out) { set_error("poms_op_rjacobi0: null argument"); return 1; }
+    const bool ws = sums_out != nullptr;
+    OpLaunch l{EPI_RJACOBI0, r, x_out, q, 0, op->L.n[0], stream, omega, ws, ws};
+    l.y2 = r_new;
+    l.beta_dev = alpha_dev;
+    if (op_run_epi(op, l)) return 1;
+    if (!ws) return 0;
+    const int64_t n = op->last_partials;   // (||dr_2||^2, ||x1||^2, ||r_new||^2: n partials each)
+    const double* scr = op->ctx->scratch;
+    if (reduce_launch(scr, (int)n, sums_out, as_stream(stream)) ||
+        reduce_launch(scr + n, (int)n, sums_out + 1, as_stream(stream)) ||
+        reduce_launch(scr + 2 * n, (int)n, sums_out + 2, as_stream(stream))) {
+        set_error("poms_op_rjacobi0: reduction launch failed");
+        return 1;
+    }
+    POMS_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int poms_op_rjacobi0_count(poms_op* op, int64_t* count, int64_t* exact) {
+    if (!op || !count) { set_error("poms_op_rjacobi0_count: null argument"); return 1; }
+    *count = op->rfold_launches;
+    if (exact) *exact = op->rfold_exact;
     return 0;
 }
 

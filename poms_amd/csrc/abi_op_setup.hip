@@ -611,7 +611,7 @@ int poms_op_galerkin_stencil(poms_op* fine, const poms_layout* coarse_layout, co
 int poms_op_destroy(poms_op* o) {
     if (!o) return 0;
     for (double* p : {o->a0t, o->b0t, o->a1, o->b1, o->a2, o->b2, o->dg2a, o->dg2b, o->rdiag0, o->coef, o->sv_dev,
-                      o->spec_dev, o->spec_bak, o->la_raw})
+                      o->spec_dev, o->spec_bak, o->la_raw, o->rf_raw})
         if (p) (void)hipFree(p);
     for (void* p : o->mf_tabs)
         if (p) (void)hipFree(p);

@@ -20,8 +20,11 @@ enum Epi : int { EPI_APPLY = 0, EPI_RESID = 1, EPI_JACOBI = 2,
                  EPI_JACOBI2 = 6,   /* two sweeps from x in one launch (2D, kron_2d.hip) */
                  EPI_JACOBI3Z = 7,  /* sweeps 1-3 from x = 0 in one launch (2D, kron_2d.hip) */
                  EPI_CHEBY = 8,     /* y = x + beta (x - y) + omega (b - A x)/diag (general forms) */
-                 EPI_PAPPLYDOT = 9  /* y2 = b + beta x, y = A y2 and per-block sums of y2 . y: pcg's p update
-                                       formed inside the next apply + dot (v5, 16-wave tiles) */ };
+                 EPI_PAPPLYDOT = 9, /* y2 = b + beta x, y = A y2 and per-block sums of y2 . y: pcg's p update
+                                       formed inside the next apply + dot (v5, 16-wave tiles) */
+                 EPI_RJACOBI0 = 10  /* y2 = x - alpha b, then EPI_JACOBI0 on y2, and per-block sums of y2 . y2
+                                       behind partial2: pcg's r update formed inside the first psolve launch
+                                       (v5, p = 3, 16-wave tiles) */ };
 
 // Geometry of one fused Kronecker launch (all extents local to this rank's slab).
 struct KronGeom {
@@ -215,8 +218,9 @@ struct KronPtrs {
     double* partial;    // Jacobi: per-block sums of dr.dr (or null)
     double* partial2;   // Jacobi: per-block sums of x_out.b (or null)
     const double* rdiag0 = nullptr;  // 1/diag(A) per global plane inside the axis-1/2 Toeplitz interior
-    double* y2 = nullptr;            // EPI_PAPPLYDOT: where b + beta x is stored (interior points only)
-    const double* beta = nullptr;    // EPI_PAPPLYDOT: beta (device)
+    double* y2 = nullptr;            // EPI_PAPPLYDOT: where b + beta x is stored (interior points only);
+                                     // EPI_RJACOBI0: where x - alpha b is
+    const double* beta = nullptr;    // EPI_PAPPLYDOT: beta (device); EPI_RJACOBI0: alpha
 };
 
 // Banded LU factors of one axis of a Kronecker solve (kron_solve.hip).

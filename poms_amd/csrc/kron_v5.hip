@@ -115,7 +115,7 @@ static const int* v5_sched(int P, int epi, const KronGeom& g, const ToepConst& t
     }
     if (cs != hipStreamCaptureStatusNone) return nullptr;
     const int T1 = kron_v5_rows(P, epi, same12 ? 1 : 0), TO = g.tout;
-    const bool j0 = epi == EPI_JACOBI0;
+    const bool j0 = epi == EPI_JACOBI0 || epi == EPI_RJACOBI0;
     std::vector<double> w(nblk);
     for (int b = 0; b < nblk; ++b) {
         const V5Tile t = v5_tile_decode(g, b);

@@ -214,7 +214,9 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     constexpr bool PAPD = (EPI == EPI_PAPPLYDOT);
     constexpr bool APD = (EPI == EPI_APPLYDOT) || PAPD;
     // two sweeps from x = 0: the x ring holds b, scaled on the fly to x1 = omega b / diag
-    constexpr bool J0 = (EPI == EPI_JACOBI0);
+    // RJ0: J0 on y2 = x - alpha b, formed in the x ring (see rj0_combine below)
+    constexpr bool RJ0 = (EPI == EPI_RJACOBI0);
+    constexpr bool J0 = (EPI == EPI_JACOBI0) || RJ0;
     constexpr bool HIST = APD || (JAC && XH) || J0;   // x (J0: x1) at the output point from a register history
     constexpr bool XIN = JAC && !XH;            // ... or DMA'd next to b (fewer VGPRs, 8 B/DOF more reads)
     constexpr bool ZR = J0;                     // zeroed rings + every-lane sums (see below)
@@ -233,6 +235,8 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     static_assert(D >= 3 || !HASB, "the b ring's wait count assumes x(t) was issued before b(t)");
     static_assert(!PAPD || (NW == 16 && NXM == 2 && D == 4 && MODE == 0),
                   "PAPD: 16-wave tiles (every wave owns one output row of the x tile), x three planes ahead");
+    static_assert(!RJ0 || (P == 3 && NW == 16 && NXM == 2 && D == 3 && MODE == 0 && SAME12),
+                  "RJ0: the p = 3 16-wave tiles, x two planes ahead (the fourth ring slot is the staging plane)");
     typedef double d2 __attribute__((ext_vector_type(2)));
 
     constexpr int XS_OFF = 0;
@@ -243,7 +247,8 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     // PAPD: the b rows (pcg's s) of the two planes DMA'd but not yet combined; every wave
     // reads back only the rows it DMA'd itself
     constexpr int SS_OFF = XS_OFF + D * XR * TC;
-    constexpr int BS_OFF = SS_OFF + (PAPD ? 2 * XR * TC : 0);
+    // RJ0: one staging plane, the b rows (pcg's q) of the plane combined next
+    constexpr int BS_OFF = SS_OFF + (PAPD ? 2 * XR * TC : RJ0 ? XR * TC : 0);
     constexpr int XI_OFF = BS_OFF + (HASB ? NB * T1 * TC : 0);
     constexpr int C2_OFF = XI_OFF + (XIN ? 2 * T1 * TC : 0);
     constexpr int RED_OFF = C2_OFF + 2 * W * TC;
@@ -266,7 +271,9 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     constexpr bool J0NX = J0 && (MODE == 4 || MODE == 5);
     constexpr int JS_OFF = (D1_OFF + (J0 ? 2 * XR : 0) + 1) & ~1;
     // J0: a row of ones, the post-axis-1 scale of the planes / tiles scaled in the ring
-    constexpr int ONE_OFF = JS_OFF + (JSL ? 2 * NW * 64 : 0);
+    // RJ0: a third per-lane running sum (||y2||^2 over the wave's stored row) behind the two
+    constexpr int JS3_OFF = JS_OFF + (JSL ? 2 * NW * 64 : 0);
+    constexpr int ONE_OFF = JS3_OFF + (RJ0 ? NW * 64 : 0);
     constexpr int LDS_N = ONE_OFF + (J0 ? TC : 0);
     __shared__ __attribute__((aligned(16))) double lds[LDS_N];
 
@@ -389,9 +396,9 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     const uint32_t arr_bytes = (uint32_t)((int64_t)nsp * g.s0 * 8);
     const uint32_t plane8 = (uint32_t)(g.s0 * 8);
     const __amdgpu_buffer_rsrc_t rx = make_rsrc(x, arr_bytes);
-    const __amdgpu_buffer_rsrc_t rbv = make_rsrc(bvec, (HASB || PAPD) ? arr_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t rbv = make_rsrc(bvec, (HASB || PAPD || RJ0) ? arr_bytes : 0u);
     const __amdgpu_buffer_rsrc_t ry = make_rsrc(y, arr_bytes);
-    const __amdgpu_buffer_rsrc_t ry2 = make_rsrc(y2, PAPD ? arr_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t ry2 = make_rsrc(y2, (PAPD || RJ0) ? arr_bytes : 0u);
     auto zo_of = [&](int t) { return max(z0 - 2 * P + t, z0); };
     // storage column of lane-column 0 (pads == P): c0 - H + P
     const int colb = (c0 - H + P) * 8 + 16 * lane;
@@ -465,7 +472,8 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
     // in the driver's bench line (round-4 verdict).
     if constexpr (ZR && (MODE == 0 || MODE == 6)) {
         // (x ring, then b and x_in rings: contiguous from XS_OFF)
-        static_assert(BS_OFF == SS_OFF && XI_OFF == BS_OFF + (HASB ? NB * T1 * TC : 0), "ring layout");
+        // (RJ0: its staging plane too -- the lane-columns no DMA fills combine to 0 - alpha 0)
+        static_assert(BS_OFF == SS_OFF + (RJ0 ? XR * TC : 0) && XI_OFF == BS_OFF + (HASB ? NB * T1 * TC : 0), "ring layout");
         constexpr int NZ = (XI_OFF + (XIN ? 2 * T1 * TC : 0) - XS_OFF) / 2;
 #pragma unroll 1
         for (int e = tid; e < NZ; e += NW * 64) *(d2*)(lds + XS_OFF + 2 * e) = d2{0.0, 0.0};
@@ -483,6 +491,7 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
         for (int e = tid; e < XR * TC; e += NW * 64)
             lds[RS_OFF + e] = j0_scale(e / TC, e % TC, tc.t0a[0], tc.t0b[0]);
         if constexpr (JSL) *(d2*)(lds + JS_OFF + 2 * tid) = d2{0.0, 0.0};
+        if constexpr (RJ0) lds[JS3_OFF + tid] = 0.0;
         if (tid < TC) lds[ONE_OFF + tid] = 1.0;
         __syncthreads();
     }
@@ -563,6 +572,67 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
         papd_combine(0);
         dma_s(2);
     }
+    // ---- RJ0: the ring holds y2 = fma(-alpha, b, x) (pcg: r_new = r - alpha q, V_RUPD's fma), the
+    // right-hand side of the two sweeps from zero.  As PAPD's combine, with a 3-deep ring (x two
+    // planes ahead) and ONE staging plane: J0's tables leave no room for more.  A wave combines
+    // the x-tile rows it DMA'd itself one plane ahead of the plane being computed, after its own
+    // vmcnt wait, writes the result over x in the ring and only then DMAs the next plane's b rows
+    // into the staging rows it has just read.  Its one output row of the x tile goes to y2 on the
+    // planes the chunk owns, the tile's output columns only, and the squares of what it stores go
+    // into the wave's third running sum (tile order: the host uses it for a guarded decision only).
+    // Loads per wave, in issue order (X, B: the n = 1 or 2 row DMAs of a plane's x, b):
+    //   X0 X1 B0 [combine 0] B1 | t = 0: X2 [combine 1] B2 | t = 1: X3 [combine 2] B3 | ...
+    // The combine of plane t+1 waits for B(t+1) (X(t+1) is older); only X(t+2) was issued after
+    // it: vmcnt(n) at every t; combine 0: B0 is the youngest, vmcnt(0).
+    double ralpha = 0.0;
+    if constexpr (RJ0) ralpha = betap[0];
+    auto dma_q = [&](int pl) { dma_rows(rbv, SS_OFF, pl < nplanes ? z0 - P + pl : -(1 << 20), 0); };
+    auto rj0_combine = [&](int pl) {    // march plane pl (local plane z0 - P + pl)
+        if (pl >= nplanes) return;      // (a dummy past the march)
+        __asm__ volatile("" ::: "memory");   // (no LDS read moves above the caller's vmcnt wait)
+        const int m = z0 - P + pl;
+        const bool own = m >= z0 && m < z1;
+        double* xr = lds + XS_OFF + (pl % D) * XR * TC + 2 * lane;
+        const double* sr = lds + SS_OFF + 2 * lane;
+        auto combine_row = [&](int row) {
+            d2 a = *(const d2*)(xr + row * TC);
+            const d2 s = *(const d2*)(sr + row * TC);
+            a[0] = __builtin_fma(-ralpha, s[0], a[0]);
+            a[1] = __builtin_fma(-ralpha, s[1], a[1]);
+            *(d2*)(xr + row * TC) = a;
+            return a;
+        };
+        // the wave's rows: wv and, on the first XR - NW waves, wv + NW; its output row is x-tile row
+        // wv at wv >= P, else wv + NW.  The other row first, so that the store is written once.
+        if (xtra) combine_row(wv >= P ? wv + NW : wv);
+        const int row = wv >= P ? wv : wv + NW;
+        const d2 a = combine_row(row);
+        if (own && r0 + row - P < g.n1) {
+            // (the epilogue's row offset plus a scalar: no second per-lane offset held through the march)
+            const int vo = ((orow + P) * s1 * 8 + colb) + ((row - wv - P) * s1 * 8 + (m + g.pd0) * (int)plane8);
+            const int vs = (cok & 1) ? vo : 0x7ffffff0;
+            const double a0 = (cok & 1) ? a[0] : 0.0;
+            const double a1 = (cok & 2) ? a[1] : 0.0;   // (past n2: a ghost or dead pitch column stays 0)
+            if constexpr (ST16) {
+                bstore2_sp<YAUX>(ry2, vs, 0u, a[0], a1);
+            } else {
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, a[0]), ry2, vs, 0, YAUX);
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, a1), ry2,
+                                                      (cok & 1) ? vo + 8 : 0x7ffffff0, 0, YAUX);
+            }
+            double s3 = lds[JS3_OFF + tid];   // this lane's own slot
+            s3 = fma(a0, a0, s3);
+            s3 = fma(a1, a1, s3);
+            lds[JS3_OFF + tid] = s3;
+        }
+        __asm__ volatile("" ::: "memory");   // (the staging rows are re-filled only after these reads)
+    };
+    if constexpr (RJ0) {
+        dma_q(0);
+        wait_vm<0>();
+        rj0_combine(0);
+        dma_q(1);
+    }
     for (int tb = 0; tb < nplanes; tb += NS) {
 #pragma unroll
         for (int q = 0; q < NS; ++q) {
@@ -589,7 +659,7 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
                     if (t == 0) wait_vm<0>();
                     else if (xtra) wait_vm<NXM>();
                     else wait_vm<NXM - 1>();
-                } else if constexpr (PAPD) {
+                } else if constexpr (PAPD || RJ0) {
                     // plane t was waited for and combined one plane ago: the barrier below
                     // waits for this wave's ring writes instead
                 } else {
@@ -602,7 +672,7 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
                     st_b = __builtin_amdgcn_s_memtime();
                     st_wait += st_b - st_a;
                 }
-                if constexpr (PAPD) v5_lds_barrier();
+                if constexpr (PAPD || RJ0) v5_lds_barrier();
                 else v5_barrier();
                 // Every wave starts the plane at a high issue priority and drops it for
                 // the plane's axis-0 scatter and epilogue.  A SIMD's four waves otherwise
@@ -631,6 +701,12 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
                     }
                     papd_combine(t + 1);
                     dma_s(t + PFX);
+                }
+                if constexpr (RJ0) {    // (the count: see rj0_combine)
+                    if (xtra) wait_vm<NXM>();
+                    else wait_vm<NXM - 1>();
+                    rj0_combine(t + 1);
+                    dma_q(t + 2);
                 }
 
                 // J0: the ring holds b; x1 = s b with s = omega / diag.  On a row-Toeplitz tile
@@ -997,6 +1073,21 @@ kron_v5_kernel(const double* __restrict__ x, double* __restrict__ y, const doubl
                 partial2[slot_of()] = s;
             }
         }
+        if constexpr (RJ0) {
+            if (partial2 != nullptr) {   // ||y2||^2, tile order: one more region of gridDim.x sums behind partial2's
+                double s3 = lds[JS3_OFF + tid];
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) s3 += __shfl_xor(s3, off, 64);
+                __syncthreads();
+                if (lane == 0) lds[RED_OFF + wv] = s3;
+                __syncthreads();
+                if (tid == 0) {
+                    double s = 0.0;
+                    for (int w = 0; w < NW; ++w) s += lds[RED_OFF + w];
+                    partial2[gridDim.x + slot_of()] = s;
+                }
+            }
+        }
     }
 }
 
@@ -1061,7 +1152,8 @@ static int v5_launch(const V5Launch& a) {
     constexpr bool JAC = EPI == EPI_JACOBI;
     const bool st16 = ((reinterpret_cast<uintptr_t>(a.p.y) + 8 * (int64_t)(a.g.pd2 - a.H)) & 15) == 0 &&
                       a.g.s1 % 2 == 0 && a.g.s0 % 2 == 0 &&
-                      (EPI != EPI_PAPPLYDOT || ((reinterpret_cast<uintptr_t>(a.p.y2) + 8 * (int64_t)(a.g.pd2 - a.H)) & 15) == 0);
+                      ((EPI != EPI_PAPPLYDOT && EPI != EPI_RJACOBI0) ||
+                       ((reinterpret_cast<uintptr_t>(a.p.y2) + 8 * (int64_t)(a.g.pd2 - a.H)) & 15) == 0);
     if (MODE != 0 && !a.same12) {   // diagnostic builds: the cubic headline grid only
         set_error("v5 diag mode: needs equal axis-1 / axis-2 Toeplitz rows");
         return 1;
@@ -1070,7 +1162,12 @@ static int v5_launch(const V5Launch& a) {
         constexpr bool ST16 = decltype(st16_c)::value, JDOT = decltype(jdot_c)::value;
         constexpr int DD = (JAC && !ST16 && D > 3) ? 3 : D;
         constexpr bool XHH = (JAC && !ST16) ? false : XH;
-        if constexpr (MODE == 0) {
+        if constexpr (EPI == EPI_RJACOBI0) {   // (one set of Toeplitz rows only: rfold_ok)
+            if (!a.same12) {
+                set_error("v5: r update + two sweeps from zero needs equal axis-1 / axis-2 Toeplitz rows");
+                return 1;
+            }
+        } else if constexpr (MODE == 0) {
             if (!a.same12) return v5_launch_kernel<P, EPI, DD, MODE, CP, XHH, ST16, JDOT, false>(a);
         }
         return v5_launch_kernel<P, EPI, DD, MODE, CP, XHH, ST16, JDOT, true>(a);
@@ -1108,7 +1205,9 @@ static int v5_launch(const V5Launch& a) {
 //     stored as y; the 16-wave builds only (its combine gives every wave one output row
 //     of the x tile);
 //   * two sweeps from zero: x ring = b (read once), scaled to x1 as it is read; y = x2
-//     streamed.
+//     streamed;
+//   * the same on y2 = x - alpha b formed in the ring (p = 3, 16-wave tiles): a 3-deep ring
+//     and one staging plane in the fourth slot's place, J0's policies, y2 stored as y.
 struct V5Build {
     int epi;
     int pmin, pmax;   // the degrees the row covers
@@ -1127,6 +1226,7 @@ constexpr V5Build kV5Production[] = {
     {EPI_APPLYDOT, 1, 5, -1, 4, CP_B_NT | CP_Y_NT, false},
     {EPI_PAPPLYDOT, 1, 3, -1, 4, CP_B_NT | CP_Y_NT, false},
     {EPI_JACOBI0, 1, 5, -1, 4, CP_B_NT | CP_Y_NT | CP_OWN_NT, false},
+    {EPI_RJACOBI0, 3, 3, -1, 3, CP_B_NT | CP_Y_NT | CP_OWN_NT, false},
 };
 constexpr int kV5NProduction = (int)(sizeof(kV5Production) / sizeof(kV5Production[0]));
 

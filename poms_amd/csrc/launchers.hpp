@@ -42,7 +42,9 @@ enum VecOp : int { V_AXPBY = 0, V_SCALE = 1, V_FILL = 2, V_DOT = 3, V_PCGUPD = 4
                   V_FINUPD = 8 /* pcg's last iteration, see stop_update */,
                   // pcg's deferred x updates (flat kernel only; pcg_native.hip)
                   V_PUPD = 9 /* z = x + b y: V_XPUPD's p into another buffer, its x untouched */,
-                  V_RNORM = 10 /* V_RUPD's r.r without the store of r */ };
+                  V_RNORM = 10 /* V_RUPD's r.r without the store of r */,
+                  V_SQNORM = 11 /* w.w with V_RUPD's grid, per-thread order and partials: on a stored
+                                   r - a q the bits of V_RUPD's sum */ };
 
 int vec_launch(int op, const RowGeom& g, double a, double b, const double* x, const double* y,
                double* z, double* w, const double* q, double* partial, hipStream_t st,

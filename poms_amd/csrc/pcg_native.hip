@@ -43,9 +43,11 @@ static double host_reduce(const double* p, int n) {
 }
 
 // The sums `pk` (PcgSlots::pkind's bits) of a region of n blocks' partials into out:
-// [dot, norm], or the three sums of EPI_JACOBI3Z.
+// [dot, norm], or the three sums of EPI_JACOBI3Z; with bit 3 (EPI_RJACOBI0) a third sum
+// behind [dot, norm], its partials behind the dots'.
 static void reduce_region(const double* reg, int n, int pk, double* out) {
     const bool wn = pk & 1, wd = pk & 2;
+    if (pk & 8) out[2] = host_reduce(reg + (size_t)2 * n, n);
     for (int i = 0; (pk & 4) && i < 3; ++i) out[i] = host_reduce(reg + (size_t)i * n, n);
     if (pk & 4) return;
     if (wn) out[wd ? 1 : 0] = host_reduce(reg, n);
@@ -61,7 +63,8 @@ static void reduce_region(const double* reg, int n, int pk, double* out) {
 // per-block partial sums into (no reduction launch: the host adds them in the
 // reduction kernel's order when it reads the slot).  npart[i] = blocks of the
 // launch that last used region i (0: none pending), pkind[i] bit 0 norm
-// partials at [0, n), bit 1 dot partials after them, bit 2 three sums (EPI_JACOBI3Z).
+// partials at [0, n), bit 1 dot partials after them, bit 2 three sums (EPI_JACOBI3Z),
+// bit 3 (with bits 0 and 1) a third sum's partials at [2n, 3n) (EPI_RJACOBI0).
 // (With a communicator only `host` is used, at fixed indices: PcgRun::hslot.)
 struct PcgSlots {
     static constexpr int kSvRing = 48, kSvPart = 4096;
@@ -171,7 +174,9 @@ struct PcgSlots {
         *out = *v;
         return 0;
     }
-    static int pk_nsum(int pk) { return (pk & 4) ? 3 : ((pk & 1) ? 1 : 0) + ((pk & 2) ? 1 : 0); }   // sums of kind pk
+    static int pk_nsum(int pk) {   // sums of kind pk
+        return (pk & 4) ? 3 : ((pk & 1) ? 1 : 0) + ((pk & 2) ? 1 : 0) + ((pk & 8) ? 1 : 0);
+    }
     static bool part_unset(const double* v) { return *reinterpret_cast<const volatile uint64_t*>(v) == kPartUnset; }
     static void part_arm(double* v, int n) {
         volatile uint64_t* q = reinterpret_cast<volatile uint64_t*>(v);
@@ -507,7 +512,8 @@ struct PcgRun {
         if ((pk & 4) ? (reduce_launch(scr, (int)n, d, st) || reduce_launch(scr + n, (int)n, d + 1, st) ||
                         reduce_launch(scr + 2 * n, (int)n, d + 2, st))
                      : ((wn && reduce_launch(scr, (int)n, d + (wd ? 1 : 0), st)) ||
-                        (wd && reduce_launch(scr + n, (int)n, d, st)))) {
+                        (wd && reduce_launch(scr + n, (int)n, d, st)) ||
+                        ((pk & 8) && reduce_launch(scr + 2 * n, (int)n, d + 2, st)))) {
             set_error("poms_pcg_jacobi: reduction launch failed");
             return 1;
         }
@@ -523,6 +529,54 @@ struct PcgRun {
         PartRoute rt{sv.region(h), ((wn ? 1 : 0) + (wd ? 1 : 0)) * PcgSlots::host_partials_max()};
         if (launch(epi, x, y, b, wn, wd, &rt)) return 1;
         return sums_tail(op->last_partials, (wn ? 1 : 0) | (wd ? 2 : 0), rt.used, h, -1, sv.host + h);
+    }
+    // ---- the r update formed inside the first psolve launch (EPI_RJACOBI0) ----
+    // Where that launch runs (rfold_ok) and the loop asks for it (poms_pcg_opts.fold_r), an
+    // iteration queues no r update: its damped_jacobi starts with r_new = r - alpha q and the
+    // two sweeps from zero on r_new in one pass -- V_RUPD's fma, J0's tiles and partial slots:
+    // the same bits -- and r_new goes to the other of two r buffers (the launch reads r's halo
+    // rows while its neighbours store theirs).  r.r comes back as a sum in tile order, fr_t,
+    // which only decides (see the loop); V_RUPD's own sum is formed from the stored r_new by
+    // V_SQNORM where its bits are needed.
+    const double *fr_old = nullptr, *fr_q = nullptr;
+    double* fr_new = nullptr;   // not null: the next damped_jacobi call starts with the fused launch
+    double fr_t = 0.0;
+    static bool rfold_on() {    // POMS_PCG_RFOLD=0: always the two launches (A-B; read per call: the
+        const char* e = getenv("POMS_PCG_RFOLD");   // tests run both in one process)
+        return !(e && e[0] == '0');
+    }
+    // [||x1||^2, ||dr_2||^2, ||r_new||^2 (tile order)] into slots h .. h+2
+    int jrun_r(double* y, int h) {
+        PartRoute rt{sv.region(h), std::min<int64_t>(3 * PcgSlots::host_partials_max(), PcgSlots::kSvPart)};
+        OpLaunch l{EPI_RJACOBI0, fr_old, y, fr_q, 0, n0, stv, o->omega, true, true, &rt};
+        l.y2 = fr_new;
+        l.beta_dev = sc + SC_ALPHA;
+        if (op_run_epi(op, l)) return 1;
+        return sums_tail(op->last_partials, 1 | 2 | 8, rt.used, h, -1, sv.host + h);
+    }
+    // r.r of the stored r with V_RUPD's bits -> host slot h (rupd's partials and reduction)
+    int sqnorm(double* r, int h) {
+        int nb = 0;
+        ++op->rfold_exact;
+        if (vec_flat_blocks(dcount, r + doff) <= PcgSlots::host_partials_max()) {
+            if (vec_flat_launch(V_SQNORM, dcount, 0.0, 0.0, nullptr, nullptr, nullptr, r + doff, nullptr, sv.region(h),
+                                st, &nb)) {
+                set_error("pcg: exact r.r pass not launched");
+                return 1;
+            }
+            POMS_HIP_CHECK(hipGetLastError());
+            sv.pending(h, nb, 1);
+            return 0;
+        }
+        // (not the scratch: the last sweep's x . rhs partials wait there for beta)
+        if (vec_flat_launch(V_SQNORM, dcount, 0.0, 0.0, nullptr, nullptr, nullptr, r + doff, nullptr, op->rf_part,
+                            st, &nb)) {
+            set_error("pcg: exact r.r pass not launched");
+            return 1;
+        }
+        reduce_wide_launch(op->rf_part, nb, sv.host + h, st);   // (as vec_common reduces V_RUPD's partials)
+        POMS_HIP_CHECK(hipGetLastError());
+        return 0;
     }
     // sweeps 1-3 from x = 0 (one rank): [||x1||^2, ||dr_2||^2, ||dr_3||^2] into slots h .. h+2
     int jrun3(const double* rhs, double* y, int h) {
@@ -716,7 +770,7 @@ struct PcgRun {
         int cur = 0;                              // buffer of the latest queued x
         // an open stop test: a sweep's norm in slot h; the from-zero pair; a two-sweep
         // launch from bufs[in]; sweeps 1-3 from zero
-        enum PendKind { P_SWEEP, P_ZERO2, P_PAIR, P_ZERO3 };
+        enum PendKind { P_SWEEP, P_ZERO2, P_PAIR, P_ZERO3, P_ZERO2R /* P_ZERO2 with the folded r update's sum */ };
         struct Pend { PendKind kind; int h, buf, in; };
         Pend q[2];
         int nq = 0, ring = 0, k0;
@@ -729,12 +783,19 @@ struct PcgRun {
             if (jrun3(rhs, A, h0)) return 1;
             q[nq++] = Pend{P_ZERO3, h0, 0, -1};
             k0 = 4;
+        } else if (fz && fr_new) {   // ... on rhs = fr_old - alpha fr_q, formed by the same launch
+            if (rhs != fr_new) { set_error("pcg: the folded r update is not the psolve's right-hand side"); return 1; }
+            const int h0 = arm(H_J0, 3);
+            if (jrun_r(A, h0)) return 1;
+            q[nq++] = Pend{P_ZERO2R, h0, 0, -1};
+            k0 = 3;
         } else if (fz) {   // sweeps 1, 2 from x = 0 in one pass over rhs: [||x1||^2, ||dr2||^2]
             const int h0 = arm(H_J0, 2);
             if (jrun(EPI_JACOBI0, rhs, A, rhs, true, true, h0)) return 1;
             q[nq++] = Pend{P_ZERO2, h0, 0, -1};
             k0 = 3;
         } else {
+            if (fr_new) { set_error("pcg: the folded r update needs the two sweeps from zero"); return 1; }
             if (maxit < 1) { set_error("pcg: jacobi maxiter < 1"); return 1; }
             const int h = arm(H_JN, 1);
             if (diag_scale_norm(rhs, A, h)) return 1;
@@ -746,9 +807,13 @@ struct PcgRun {
         // returns 0; S_ERR: the call returns 1 (the values are damped_jacobi's returns).
         enum Settled { S_OPEN = -1, S_DONE = 0, S_ERR = 1 };
         auto settle = [&]() -> Settled {
-            const Pend f = q[0];
+            Pend f = q[0];
             q[0] = q[1];
             --nq;
+            if (f.kind == P_ZERO2R) {   // r.r in tile order, read with the launch's other sums
+                fr_t = get(f.h, 2);
+                f.kind = P_ZERO2;
+            }
             double* res = nullptr;
             // a stop before the launch's last sweep: that iterate is re-formed into the buffer
             // the next launch wrote (abandoned; queued after every sweep that reads it)
@@ -1076,6 +1141,30 @@ static int pcg_setup_lookahead(poms_op* op, const double* like, hipStream_t st) 
     return 0;
 }
 
+// The folded r update's second r buffer, op->rf_buf: placed and zeroed as the lookahead's
+// buffer above (`like` is the call's r).
+static int pcg_setup_rfold(poms_op* op, const double* like, hipStream_t st) {
+    const int64_t nbuf = padded_len(op);
+    const int64_t off = (int64_t)((reinterpret_cast<uintptr_t>(like) & 127) / sizeof(double));
+    if (op->rf_n < nbuf) {
+        if (op->rf_raw) POMS_HIP_CHECK(hipFree(op->rf_raw));
+        op->rf_raw = op->rf_buf = op->rf_part = nullptr;
+        op->rf_n = 0;
+        // (behind the vector: the exact r.r pass's partials where they do not fit a host region --
+        // the scratch holds the last sweep's x . rhs partials for beta by then)
+        POMS_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&op->rf_raw), (nbuf + 16 + kScratch) * sizeof(double)));
+        op->rf_part = op->rf_raw + nbuf + 16;
+        op->rf_n = nbuf;
+        op->rf_off = -1;
+    }
+    if (op->rf_off != off) {   // (re-)placed: zero ghosts
+        POMS_HIP_CHECK(hipMemsetAsync(op->rf_raw, 0, (nbuf + 16) * sizeof(double), st));
+        op->rf_off = off;
+        op->rf_buf = op->rf_raw + off;
+    }
+    return 0;
+}
+
 static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o, const double* b, double* x,
                            int has_x0, double* const* work, poms_pcg_info* info, void* stream) {
     if (!op || !o || !b || !x || !work || !info) { set_error("poms_pcg_jacobi: null argument"); return 1; }
@@ -1158,12 +1247,63 @@ static int pcg_jacobi_impl(poms_op* op, poms_comm* comm, const poms_pcg_opts* o,
     int k = 0;
     int pring = 0;   // deferred: the p buffer p_{k+1} goes to
     double nrmr = nrmr0 * nrmr0;
+    // The r update folded into the first psolve launch (poms_pcg_opts.fold_r; PcgRun::fr_*): the
+    // deferred path under skip_tail only, where the loop's last iteration forms r.r exactly
+    // (V_RNORM) whatever the iterations before it did, and where EPI_RJACOBI0 runs on these
+    // vectors.  r then alternates between work[0] and op->rf_buf.
+    // The stop test `r.r < tol * nrmr0` is decided from the launch's sum in tile order, t, where
+    // that is safe.  Both t and V_RUPD's sum e add the same m <= dcount non-negative terms
+    // fma(r_i, r_i, .), each in some order of its own, so each is within a factor 1 +- gamma_m
+    // of the exact sum S of the r_i^2 (gamma_m = m u / (1 - m u), u = 2^-53: Higham, Accuracy and
+    // Stability of Numerical Algorithms, 4.2; the fma rounds once per term): e >= t (1 - gamma_m)
+    // / (1 + gamma_m).  So t >= tol nrmr0 (1 + g) with g >= 2 gamma_m / (1 - gamma_m) implies
+    // e >= tol nrmr0: no stop, whatever e's bits.  g = 4 m u covers that with 2 m u to spare for
+    // the roundings of the threshold itself (m u < 0.2: m < 2^50).  Otherwise e is formed from the
+    // stored r_new by V_SQNORM -- V_RUPD's grid, order and partials: its bits -- and decides.
+    bool rfold = false;
+    if (R.defer && o->skip_tail && o->fold_r && PcgRun::rfold_on() && o->jmaxiter >= 3 && o->maxiter >= 2) {
+        if (pcg_setup_rfold(op, r, R.st)) return 1;
+        rfold = rfold_ok(op, r, q, op->rf_buf, fp[0]) && rfold_ok(op, op->rf_buf, q, r, fp[0]);
+    }
+    const double rf_g = 4.0 * (double)R.dcount * 0x1p-53;
     for (k = 1; k <= o->maxiter; ++k) {
         if (R.defer && R.push_term(p)) {   // (before the launch that forms alpha_k)
             (void)R.flush_pupd();          // (an error path: no apply follows a remembered p update)
             return 1;
         }
         if (R.apd_alpha(p, q)) return 1;
+        if (rfold && k < o->maxiter) {
+            if (R.flush_alpha()) return 1;   // (alpha at sc[SC_ALPHA], as the unfolded r update reads it there)
+            double* rn = r == work[0] ? op->rf_buf : work[0];
+            R.fr_old = r;
+            R.fr_q = q;
+            R.fr_new = rn;
+            double* sn = nullptr;
+            const int rc = R.damped_jacobi(rn, fp[0], fp[1], SC_SRN, &sn, &dd, fp[2]);
+            R.fr_new = nullptr;
+            if (rc) return 1;
+            r = rn;
+            if (!dd && R.dot(sn, r, R.sc + SC_SRN)) return 1;
+            if (R.failed) return 1;
+            const double thr = o->tol * nrmr0;
+            if (!(R.fr_t >= thr * (1.0 + rf_g))) {   // inside the guard band (or not a number): V_RUPD's own sum decides
+                const int hx = R.arm(H_RR, 1);
+                if (R.sqnorm(r, hx)) return 1;
+                nrmr = R.get(hx);
+                if (R.failed) return 1;
+                if (nrmr < o->tol * nrmr0) {   // the reference stops before psolve: that one is discarded
+                    if (R.xflush(true)) return 1;
+                    k -= 1;
+                    break;
+                }
+            }
+            double* pn = o->pbuf[pring];
+            if (R.is_pending(pn) && R.xflush(false)) return 1;
+            if (R.pupd(sn, p, pn, dd && R.dot_part_n >= 0, q)) return 1;   // (may leave it to the next apply + dot)
+            p = pn;
+            pring = (pring + 1) % npb;
+            continue;
+        }
         const int hrr = R.arm(H_RR, 1);
         if (R.defer && o->skip_tail && k == o->maxiter) {
             // the sum alone, then x with the rounding the stop test selects

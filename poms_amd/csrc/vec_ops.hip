@@ -114,6 +114,9 @@ __device__ __forceinline__ void vec_elem(double a, double b, const double* x, co
     } else if constexpr (OP == V_RNORM) {
         const double rn = fma(-a, q[o], w[o]);
         s = fma(rn, rn, s);
+    } else if constexpr (OP == V_SQNORM) {
+        const double rn = w[o];
+        s = fma(rn, rn, s);
     } else if constexpr (OP == V_PUPD) {
         z[o] = x[o] + b * yv[o];
     } else if constexpr (OP == V_FINUPD) {
@@ -198,7 +201,8 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
                 if constexpr (OP == V_AXPBY || OP == V_DOT || OP == V_PCGUPD || OP == V_FINUPD || OP == V_PUPD)
                     ya[u] = ld(Y + i);
                 if constexpr (OP == V_PCGUPD || OP == V_XPUPD || OP == V_FINUPD) za[u] = ld(Z + i);
-                if constexpr (OP == V_PCGUPD || OP == V_RUPD || OP == V_XPUPD || OP == V_FINUPD || OP == V_RNORM)
+                if constexpr (OP == V_PCGUPD || OP == V_RUPD || OP == V_XPUPD || OP == V_FINUPD || OP == V_RNORM ||
+                              OP == V_SQNORM)
                     wa[u] = ld(Wv + i);
                 if constexpr (OP == V_PCGUPD || OP == V_RUPD || OP == V_FINUPD || OP == V_RNORM) qa[u] = ld(Q + i);
             }
@@ -240,6 +244,9 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
                     rn.y = fma(-a, qa[u].y, wa[u].y);
                     s = fma(rn.x, rn.x, s);
                     s = fma(rn.y, rn.y, s);
+                } else if constexpr (OP == V_SQNORM) {   // V_RUPD's sum of a stored r
+                    s = fma(wa[u].x, wa[u].x, s);
+                    s = fma(wa[u].y, wa[u].y, s);
                 } else if constexpr (OP == V_PUPD) {    // V_XPUPD's p, into z
                     d2 wn;
                     wn.x = xa[u].x + b * ya[u].x;
@@ -274,7 +281,7 @@ vec_flat_kernel(const int head, const int64_t nd2, const int tail, double a, dou
         if (tail) vec_elem<OP>(a, b, x, yv, z, w, q, head + 2 * nd2, s);
     }
     if constexpr (OP == V_DOT || OP == V_PCGUPD || OP == V_RUPD || OP == V_SCALEDOT || OP == V_FINUPD ||
-                  OP == V_RNORM) {
+                  OP == V_RNORM || OP == V_SQNORM) {
         const double t = block_sum_256(s, red);
         if (threadIdx.x == 0) partial[blockIdx.x] = t;
     }
@@ -576,6 +583,7 @@ int vec_flat_launch(int op, int64_t count, double a, double b, const double* x, 
         POMS_VF(V_FINUPD)
         POMS_VF(V_PUPD)
         POMS_VF(V_RNORM)
+        POMS_VF(V_SQNORM)
 #undef POMS_VF
     }
     return 1;

@@ -223,7 +223,8 @@ class _VCycle:
             # (_skip_tail: a smoother call's last iteration ends at x and r.r, see solvers.pcg)
             # (_defer_x: x brought up to date once per call where that pays, see solvers.defer_x_count)
             dx = defer_x_count(A, self.spaces[l], n)
-            x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=n, _skip_tail=True, _defer_x=dx)
+            x, ipre = pcg(A, damped_jacobi, b, x0=x0, tol=self.tol, maxiter=n, _skip_tail=True, _defer_x=dx,
+                          _fold_r=True)
         if self.fused[l]:
             rc = tr.resid_restrict(A, b, x, out=self.rcs[l])
         else:
@@ -251,7 +252,7 @@ class _VCycle:
         else:
             # (x is this cycle's own temporary, never the caller's x0: iterate in its buffer, no copy)
             x, ipos = pcg(A, damped_jacobi, b, x0=x, tol=self.tol, maxiter=n, _x0_owned=True, _skip_tail=True,
-                          _defer_x=dx)
+                          _defer_x=dx, _fold_r=True)
         if self.infos[l] is None:
             self.infos[l] = (ipre, ipos)
         return x

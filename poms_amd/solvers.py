@@ -71,7 +71,7 @@ def _tail_skipped(skip_tail) -> bool:
 
 
 def pcg(A, psolve, b, x0=None, tol=1e-6, maxiter=100, verbose=False, *, _x0_owned=False, _skip_tail=False,
-        _defer_x=0):
+        _defer_x=0, _fold_r=False):
     """Preconditioned conjugate gradient (`sources/solvers.py:69-135`).
 
     ``_skip_tail`` (internal: the V-cycles' smoother calls): iteration ``k == maxiter``
@@ -88,14 +88,22 @@ def pcg(A, psolve, b, x0=None, tol=1e-6, maxiter=100, verbose=False, *, _x0_owne
     the number of extra ``p`` buffers the native loop may keep, so that ``x += alpha p``
     runs as one pass per that many iterations instead of one per iteration -- the same
     fma per term, the same ``x`` and ``info``; one more vector of memory per buffer.
-    ``POMS_PCG_DEFER_X=<n>`` (read per call) replaces a non-zero count, 0 turns it off."""
+    ``POMS_PCG_DEFER_X=<n>`` (read per call) replaces a non-zero count, 0 turns it off.
+
+    ``_fold_r`` (internal: the V-cycles' smoother calls; with ``_skip_tail`` and ``_defer_x`` on
+    the native loop only): where ``A.rjacobi0_supported``, ``r -= alpha q`` is formed inside the
+    preconditioner call's first launch instead of a pass of its own, and the stop test is
+    decided from that launch's ``r . r`` unless it falls within a guard band of rounding
+    errors around the threshold, where the r update's own sum is formed and decides -- the
+    same ``x`` and ``info``; one more vector of memory.  ``POMS_PCG_RFOLD=0`` (read per call)
+    keeps the two launches."""
     _check(A, b)
     V = b.space
     skip_tail = _tail_skipped(_skip_tail)
     if (psolve is damped_jacobi and not verbose and V.lazy_reductions and A.apply_dot_supported
             and A.fused_dot_supported):
         if _native_ok(A, V):
-            return _pcg_native(A, b, x0, tol, maxiter, _x0_owned, skip_tail, _defer_x)
+            return _pcg_native(A, b, x0, tol, maxiter, _x0_owned, skip_tail, _defer_x, bool(_fold_r))
         return _pcg_device(A, b, x0, tol, maxiter, skip_tail)
     ctx, lay = V.ctx, V.layout
     if x0 is None:
@@ -253,7 +261,7 @@ def _defer_buffers(A, V, n):
     return bufs[:n]
 
 
-def _pcg_native(A, b, x0, tol, maxiter, x0_owned=False, skip_tail=False, defer_x=0):
+def _pcg_native(A, b, x0, tol, maxiter, x0_owned=False, skip_tail=False, defer_x=0, fold_r=False):
     """pcg(A, damped_jacobi, b, x0, tol, maxiter) as one C call (``poms_pcg_jacobi``):
     the launches, device scalars and stop tests of :func:`_pcg_device`, bitwise the
     same iterates, without a Python round trip per launch."""
@@ -276,6 +284,7 @@ def _pcg_native(A, b, x0, tol, maxiter, x0_owned=False, skip_tail=False, defer_x
     if pbufs:
         pptrs = (C.c_void_p * len(pbufs))(*[w._data.data_ptr() for w in pbufs])
         opts.n_pbuf, opts.pbuf = len(pbufs), pptrs
+    opts.fold_r = 1 if fold_r else 0
     info = _lib.PcgInfo()
     ptrs = (C.c_void_p * 5)(*[w._data.data_ptr() for w in work])
     _lib.call("poms_pcg_jacobi", A._h, d.native.h if d is not None else None,

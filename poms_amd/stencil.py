@@ -940,6 +940,38 @@ class KronOperator:
         _lib.call("poms_op_papply_dot_count", self._h, C.byref(v))
         return v.value
 
+    def rjacobi0_supported(self, r: StencilVector, q: StencilVector, r_new: StencilVector,
+                           x_out: StencilVector) -> bool:
+        """Whether :meth:`rjacobi0` runs on these vectors (``poms_op_rjacobi0_supported``)."""
+        self._check(r, q, r_new, x_out)
+        v = C.c_int()
+        _lib.call("poms_op_rjacobi0_supported", self._h, rt.ptr(r._data), rt.ptr(q._data), rt.ptr(r_new._data),
+                  rt.ptr(x_out._data), C.byref(v))
+        return bool(v.value)
+
+    def rjacobi0(self, alpha: torch.Tensor, r: StencilVector, q: StencilVector, r_new: StencilVector,
+                 x_out: StencilVector, omega: float, sums: bool = True) -> torch.Tensor | None:
+        """pcg's r update inside the two damped-Jacobi sweeps from zero that follow it, one launch
+        (``poms_op_rjacobi0``): ``r_new = r - alpha q`` and ``x_out`` = two sweeps from ``x = 0`` on
+        ``r_new``; ``alpha``: a device float64 tensor of one element.  With ``sums`` a device tensor
+        ``[||dr_2||^2, ||x1||^2, r_new . r_new]``, the last one added in the order of the launch's
+        tiles.  Only the interior of ``r_new`` is written: its ghosts must be zero already."""
+        self._check(r, q, r_new, x_out)
+        out = torch.zeros(3, dtype=F64, device=alpha.device) if sums else None
+        _lib.call("poms_op_rjacobi0", self._h, float(omega), rt.ptr(alpha), rt.ptr(r._data), rt.ptr(q._data),
+                  rt.ptr(r_new._data), rt.ptr(x_out._data), rt.ptr(out) if sums else None, _stream())
+        r_new._mark_written()
+        x_out._mark_written()
+        return out
+
+    @property
+    def rjacobi0_count(self) -> tuple[int, int]:
+        """Launches of :meth:`rjacobi0`'s kernel so far, the native pcg loop's included, and the
+        exact ``r . r`` passes that loop queued behind them."""
+        v, e = C.c_int64(), C.c_int64()
+        _lib.call("poms_op_rjacobi0_count", self._h, C.byref(v), C.byref(e))
+        return v.value, e.value
+
     def residual(self, b: StencilVector, x: StencilVector, out: StencilVector | None = None) -> StencilVector:
         """r = b - A x, fused (`sources/solvers.py:85`, `sources/mg_jac.py:93`)."""
         self._check(b, x)
