@@ -33,13 +33,14 @@
 extern "C" {
 #endif
 
-#define POMS_ABI_VERSION 12 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
+#define POMS_ABI_VERSION 13 /* 6: poms_op_create_matfree_tensor, poms_op_assemble_stencil_tensor;
                              * 7: poms_pcg_opts.n_pbuf, .pbuf;
                              * 8: poms_op_set_dirichlet, poms_op_get_dirichlet;
                              * 9: poms_op_cheby_step, poms_op_cheby_supported;
                              * 10: poms_op_papply_dot (+ _supported, _count), poms_pcg_p_update_dev;
                              * 11: poms_op_add_face_term, poms_op_face_terms;
-                             * 12: poms_op_rjacobi0 (+ _supported, _count), poms_pcg_opts.fold_r */
+                             * 12: poms_op_rjacobi0 (+ _supported, _count), poms_pcg_opts.fold_r;
+                             * 13: poms_block_gram, poms_block_combine */
 
 /* operator forms (see poms_op_create) */
 #define POMS_FORM_SINGLE 0 /* y = F0 (x) F1 (x) F2 x                                  */
@@ -862,6 +863,36 @@ int poms_points_deposit_atomic(poms_points* points, const double* pos, const dou
 int poms_points_deposit_binned(poms_points* points, const double* pos, const double* w, int64_t N,
                                const int64_t* perm, const int64_t* cell_start, int64_t e0b, int64_t e0e,
                                int accumulate, double* b, void* stream);
+
+/* ---- block vector algebra (ABI 13) ------------------------------------------
+ * Lists of vectors of one layout, for block methods (poms_amd.eigen's LOBPCG, block
+ * Krylov methods, several right-hand sides).  The reference has no counterpart.
+ * xs, ys, ins and outs are HOST arrays of DEVICE pointers, at most POMS_BLOCK_MAX each;
+ * they are passed to the kernels by value: a call allocates, frees and synchronises
+ * nothing.  Both run over whole interior planes like the poms_vec_* kernels (the ghost
+ * rows / columns inside them are zero in every vector and stay zero) and refuse a layout
+ * with POMS_LAYOUT_GHOST_DATA (status 1 and a message), as they do a null or misaligned
+ * pointer and a size outside its range.  Any 16-B phase of the pointers is handled
+ * (16-B accesses where all of a call's vectors share it, 8-B otherwise).               */
+#define POMS_BLOCK_MAX 24
+/* out_dev[i * ny + j] = x_i . y_j (device, nx * ny doubles, row-major), 1 <= nx, ny <=
+ * POMS_BLOCK_MAX.  Each vector is read once per 4 x 4 tile of the output it belongs to;
+ * per-block sums go to the context scratch and are added in a fixed order: no atomics,
+ * and the grid depends on the layout and (nx, ny) only, so two calls give the same
+ * bits.  symmetric != 0 (nx == ny): the caller asserts x_i . y_j == x_j . y_i (ys = xs,
+ * or ys = A xs with A symmetric); only the tiles on or above the diagonal are computed --
+ * their entries have the bits of the symmetric = 0 call -- and the strict lower triangle
+ * is copied from the upper, so the result equals its transpose bitwise.                */
+int poms_block_gram(poms_ctx* ctx, const poms_layout* layout, int nx, const double* const* xs, int ny,
+                    const double* const* ys, int symmetric, double* out_dev, void* stream);
+/* out_j = sum_i coef_dev[i * nout + j] in_i for j < nout: 1 <= nin <= POMS_BLOCK_MAX,
+ * 1 <= nout <= 16, coef_dev nin * nout doubles on the DEVICE, row-major.  Per element
+ * acc = coef[0][j] in_0, then acc = fma(coef[i][j], in_i, acc) for i = 1 .. nin-1 in that
+ * order; every input element is loaded once and feeds all nout sums.  An output may be
+ * neither an input nor another output (checked by pointer equality: status 1); the outputs'
+ * ghost planes are not written.                                                         */
+int poms_block_combine(poms_ctx* ctx, const poms_layout* layout, int nin, const double* const* ins, int nout,
+                       double* const* outs, const double* coef_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,7 @@ __all__ = [
     "MatrixFreeOperator", "MatrixFreeVCycle",
     "Mapping", "SplineMapping", "MappedDomain", "pullback",
     "DirichletBC", "RobinBC",
+    "lobpcg", "rayleigh_ritz", "block_gram", "block_combine",
 ]
 
 
@@ -70,6 +71,9 @@ def __getattr__(name):
     if name in ("DirichletBC", "RobinBC"):
         from . import boundary
         return getattr(boundary, name)
+    if name in ("lobpcg", "rayleigh_ritz", "block_gram", "block_combine"):
+        from . import eigen
+        return getattr(eigen, name)
     if name == "SlabDistribution":
         from .dist import SlabDistribution
         return SlabDistribution

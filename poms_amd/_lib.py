@@ -191,6 +191,8 @@ _SIGS = {
     "poms_points_eval": [_vp, _vp, _vp, _i64, _i, _vp, _vp],
     "poms_points_deposit_atomic": [_vp, _vp, _vp, _i64, _vp, _vp],
     "poms_points_deposit_binned": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i, _vp, _vp],
+    "poms_block_gram": [_vp, _LP, _i, _pp, _i, _pp, _i, _vp, _vp],
+    "poms_block_combine": [_vp, _LP, _i, _pp, _i, _pp, _vp, _vp],
 }
 _RESTYPES = {"poms_last_error": C.c_char_p}
 

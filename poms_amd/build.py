@@ -16,7 +16,7 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = HERE / "libpoms_hip.so"
 OBJ = HERE / "_obj"
-SOURCES = ["kron_fused.hip", "kron_dpp.hip", "kron_v4.hip", "kron_v5.hip", "kron_v5_p1.hip", "kron_v5_p2.hip", "kron_v5_p3.hip", "kron_v5_p4.hip", "kron_v5_p5.hip", "kron_v5_diag.hip", "kron_2d.hip", "vec_ops.hip", "transfer.hip", "kron_solve.hip", "stencil_general.hip", "stencil_galerkin.hip", "matfree.hip", "spline_field.hip", "spline_points.hip", "comm.hip", "pcg_native.hip", "abi_op.hip", "abi_op_setup.hip", "abi_vec.hip", "abi_transfer.hip", "abi_ksolve.hip"]
+SOURCES = ["kron_fused.hip", "kron_dpp.hip", "kron_v4.hip", "kron_v5.hip", "kron_v5_p1.hip", "kron_v5_p2.hip", "kron_v5_p3.hip", "kron_v5_p4.hip", "kron_v5_p5.hip", "kron_v5_diag.hip", "kron_2d.hip", "vec_ops.hip", "block_ops.hip", "transfer.hip", "kron_solve.hip", "stencil_general.hip", "stencil_galerkin.hip", "matfree.hip", "spline_field.hip", "spline_points.hip", "comm.hip", "pcg_native.hip", "abi_op.hip", "abi_op_setup.hip", "abi_vec.hip", "abi_block.hip", "abi_transfer.hip", "abi_ksolve.hip"]
 ARCH = os.environ.get("POMS_OFFLOAD_ARCH", "gfx950")
 
 

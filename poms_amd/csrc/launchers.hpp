@@ -76,6 +76,22 @@ int diag_scale_launch(bool is3d, int form, const RowGeom& g, int P, int g0, doub
                       double* partial, hipStream_t st, int* nblk_out);
 int dense_matvec_launch(int n, const double* M, const double* x, double* y, hipStream_t st);
 
+// ---- block_ops.hip ----------------------------------------------------------------
+// Lists of vectors over `count` doubles from each pointer (a flat range): the pointers go
+// to the kernels by value, at most kBlockMax (POMS_BLOCK_MAX) of them per list.
+constexpr int kBlockMax = 24;
+constexpr int kCombineMaxOut = 16;
+constexpr int kGramTile = 4;   // the Gram kernel's register tile: 4 x 4 sums per thread
+constexpr int kGramMaxTiles = (kBlockMax / kGramTile) * (kBlockMax / kGramTile);
+// out[i * ny + j] = x_i . y_j (symmetric: tiles on or above the diagonal only, the strict
+// lower triangle copied from the upper); per-block partials in `partial` (kScratch doubles),
+// then an ordered reduction.  1: a bad count or size, nothing launched.
+int block_gram_launch(int64_t count, int nx, const double* const* xs, int ny, const double* const* ys,
+                      int symmetric, double* partial, double* out, hipStream_t st);
+// out_j = sum_i coef[i * nout + j] in_i (coef on the device); nin <= kBlockMax, nout <= kCombineMaxOut
+int block_combine_launch(int64_t count, int nin, const double* const* ins, int nout, double* const* outs,
+                         const double* coef, hipStream_t st);
+
 // ---- stencil_general.hip ----------------------------------------------------------
 // (tensor_ndim = 2 or 3: a_q holds the component planes of a tensor coefficient, see
 // common.hpp's Tensor6; 0: a scalar field or null)
